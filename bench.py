@@ -25,10 +25,14 @@ N>1, BASELINE configs[3]'s scaling curve, two launch shapes, both row-cyclic
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--size WxH] [--samples-sqrt S]
                     [--depth D] [--scaling strong|weak] [--mode parity|fast]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
-Rank 0 prints one JSON line (contract in the task statement). After the timed
-region (N=1): the frame is hashed against the committed full-frame oracle
+Rank 0 prints one JSON line. A plain run sets up, warms up, times the K steps,
+writes the last timed frame to DIR/image.npy under `--dump-outputs DIR`, and
+prints the line (`value`, `ms_per_step`, the launch's own `stats` and the parts
+of `roofline` that need no further run). `--full` adds, after the timed region
+(N=1): the frame is hashed against the committed full-frame oracle
 fixture when one exists (`parity`), the render kernel's counters are collected by
 separate rocprofv3 --pmc passes of a one-frame child run (`roofline.valu_issue`,
 `roofline.traffic`), the one-shot ABI call with host buffers + PPM is timed
@@ -93,12 +97,19 @@ def parse():
     p.add_argument("--mode", choices=("parity", "fast"), default="parity",
                    help="parity = f64 bit-exact (the headline); fast = the f32 mode with "
                         "independent per-sample streams (statistical parity, tests/test_gpu_fast.py)")
-    p.add_argument("--cpu-baseline", type=int, default=1, help="0 disables the CPU leg")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed region also run the legs beside the headline figure: the "
+                        "parity hash against the oracle fixture, the rocprofv3 --pmc passes, the "
+                        "end-to-end call and the CPU baseline (each has its own 0/1 switch below)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="write the last timed step's frame to DIR/image.npy (f64 parity / f32 fast; "
+                        "a fixed seeded row sample when the frame is over 64 MB)")
+    p.add_argument("--cpu-baseline", type=int, default=1, help="--full: 0 disables the CPU leg")
     p.add_argument("--e2e", type=int, default=1,
-                   help="0 disables the end-to-end leg (one-shot ABI call with host buffers + PPM)")
+                   help="--full: 0 disables the end-to-end leg (one-shot ABI call with host buffers + PPM)")
     p.add_argument("--pmc", type=int, default=1,
-                   help="1: rocprofv3 --pmc passes of a one-frame child run (N=1, after the timed "
-                        "region); 0: only the build-stamped profiles/r06_pmc.json")
+                   help="--full: 1: rocprofv3 --pmc passes of a one-frame child run (N=1, after the "
+                        "timed region); 0: only the build-stamped profiles/r06_pmc.json")
     p.add_argument("--cpu-row-stride", type=int, default=0,
                    help="oracle renders every k-th row (0 = auto, ~10-30 s)")
     p.add_argument("--pmc-out", default="",
@@ -108,6 +119,8 @@ def parse():
     a = p.parse_args()
     a.width, a.height = (int(v) for v in a.size.lower().split("x"))
     a.sim = tuple(int(v) for v in a.shard_of.split(":")) if a.shard_of else None
+    if not a.full:  # a plain run: set up, warm up, time the steps, print the line
+        a.cpu_baseline = a.e2e = a.pmc = 0
     return a
 
 
@@ -336,11 +349,28 @@ def cpu_baseline(cam, sph, ns, mt, nm, s, stride, repeats=3):
                                           "direct calls"}}
 
 
+DUMP_LIMIT = 64 * 1000 * 1000  # bytes, --dump-outputs in all
+
+
+def dump_outputs(a, image):
+    """--dump-outputs: the frame the last timed step left (what a caller of the step
+    receives; gathered on rank 0 at N>1) as DIR/image.npy in its own dtype. A frame
+    over DUMP_LIMIT is cut to a fixed seeded sample of its rows, in ascending order."""
+    import numpy as np
+    fb = image.contiguous().cpu().numpy()
+    row_bytes = fb[0].nbytes
+    if fb.nbytes > DUMP_LIMIT:
+        keep = np.random.default_rng(SEED).choice(fb.shape[0], DUMP_LIMIT // row_bytes, replace=False)
+        fb = fb[np.sort(keep)]
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    np.save(os.path.join(a.dump_outputs, "image.npy"), fb)
+
+
 def parity_check(a, image, segments):
     """The timed frame against the committed oracle fixture, outside the timed region:
     the full-frame fixture (tests/golden/make_fullframe.py) when the workload has one,
     else its row sample (config 5: the sampled rows' SHA-256)."""
-    if a.mode != "parity":
+    if a.mode != "parity" or not a.full:
         return None
     full = os.path.join(HERE, "tests", "golden", f"fullframe_{workload_name(a)}.json")
     rows = os.path.join(HERE, "tests", "golden", f"rowsample_{workload_name(a)}.json")
@@ -509,7 +539,7 @@ def group_main(a, torch, rtw, shard):
     # roofline of entry 0 (its rows of the split, its kernel time): the counter child
     # renders the same rows on device 0
     n_cu = torch.cuda.get_device_properties(devs[0]).multi_processor_count
-    pm, pm_source = None, "not collected (--pmc 0)"
+    pm, pm_source = None, "not collected (a plain run, or --pmc 0)"
     if a.pmc and devs[0] == 0:
         res, why = pmc_live(a, shard=(len(devs), 0))
         kern = MAIN_KERNEL[a.mode]
@@ -521,6 +551,8 @@ def group_main(a, torch, rtw, shard):
     out["roofline"] = roofline(a, per[0], per[0].kernel_ms, per[0].main_kernel_ms, pm, pm_source, n_cu,
                                per[0].grid_blocks)
     out["roofline"]["scope"] = "entry 0 (device %d): its rows, its kernel time" % devs[0]
+    if a.dump_outputs:
+        dump_outputs(a, image)
     out["parity"] = parity_check(a, image, total.segments)
     print(json.dumps(out), flush=True)
     g.close()
@@ -610,11 +642,13 @@ def main():
     if a.sim:  # this rank's samples only
         total_samples = st.pixels * n_off * a.steps
     value = total_samples / elapsed / 1e6
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a, plan.image)
     parity = parity_check(a, plan.image, segments) if rank == 0 and not a.sim else None
 
     out = None
     if rank == 0:
-        pm, pm_source = None, "not collected (--pmc 0)"
+        pm, pm_source = None, "not collected (a plain run, or --pmc 0)"
         n_cu = torch.cuda.get_device_properties(local).multi_processor_count
         # the counter child renders what this rank rendered: the whole frame (N=1, or
         # weak scaling: rank 0's frame), or rank 0's rows of the strong split (the

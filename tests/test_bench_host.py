@@ -78,6 +78,36 @@ def test_cpu_baseline_threads_rule_is_reported():
     assert n >= 1 and "available_parallelism" in how
 
 
+def test_plain_run_has_no_legs_and_full_keeps_their_switches(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1"])
+    a = bench.parse()
+    assert (a.full, a.cpu_baseline, a.e2e, a.pmc, a.steps, a.dump_outputs) == (False, 0, 0, 0, 2, "")
+    assert bench.parity_check(a, None, 0) is None  # no hash of the frame in a plain run
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--e2e", "0"])
+    a = bench.parse()
+    assert (a.full, a.cpu_baseline, a.e2e, a.pmc) == (True, 1, 0, 1)
+
+
+def test_dump_outputs_writes_the_frame_or_a_fixed_row_sample(tmp_path, monkeypatch):
+    np = pytest.importorskip("numpy")
+    torch = pytest.importorskip("torch")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--dump-outputs", str(tmp_path / "d")])
+    a = bench.parse()
+    img = torch.arange(7 * 5 * 3, dtype=torch.float64).reshape(7, 5, 3)
+    bench.dump_outputs(a, img)
+    got = np.load(tmp_path / "d" / "image.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, img.numpy())
+    # over the limit: whole rows, the same ones every run, in image order, within the limit
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 3 * img[0].numel() * 8 + 8)
+    bench.dump_outputs(a, img)
+    first = np.load(tmp_path / "d" / "image.npy")
+    bench.dump_outputs(a, img)
+    again = np.load(tmp_path / "d" / "image.npy")
+    assert first.shape == (3, 5, 3) and np.array_equal(first, again)
+    rows = [int(r[0, 0]) // 15 for r in first]
+    assert rows == sorted(set(rows)) and all(np.array_equal(first[i], img.numpy()[r]) for i, r in enumerate(rows))
+
+
 def _rccl_probe(env_extra):
     code = ("import raytracing_in_a_weekend_rust_amd as r; ok, why = r.rccl_available(); "
             "print(int(ok)); print(why)")

@@ -33,7 +33,7 @@ def main():
     for r in range(rounds):
         for lib in libs:
             env = lib_env(lib)
-            p = subprocess.run([sys.executable, os.path.join(HERE, "bench.py"), "--steps", "3", "--warmup", "1",
+            p = subprocess.run([sys.executable, os.path.join(HERE, "bench.py"), "--full", "--steps", "3", "--warmup", "1",
                                 "--cpu-baseline", "0", "--pmc", "0", "--e2e", "0"] + os.environ.get("LIBAB_ARGS", "").split(), env=env, capture_output=True, text=True, timeout=300)
             line = [x for x in p.stdout.splitlines() if x.startswith("{")]
             if p.returncode != 0 or not line:

@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp PYTHONPATH=.
 OUT=gpurun_out/${1:-fast}
 mkdir -p $OUT
-timeout -k 10 200 python bench.py --mode fast --cpu-baseline 0 > $OUT/bench_fast.json 2> $OUT/bench_fast.err
+timeout -k 10 200 python bench.py --full --mode fast --cpu-baseline 0 > $OUT/bench_fast.json 2> $OUT/bench_fast.err
 cat $OUT/bench_fast.json
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace_fast -o run --output-format csv -- python3 bench.py --mode fast --cpu-baseline 0 > $OUT/trace_fast.log 2>&1
 echo "trace done"

@@ -13,7 +13,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout
 tail -1 $OUT/pytest_gpu.log
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
 cat $OUT/smoke.log
-timeout -k 10 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 cat $OUT/bench.json
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- python3 bench.py --cpu-baseline 0 > $OUT/trace.log 2>&1
 echo "trace done"
