@@ -122,7 +122,8 @@ const char *rtw_build_id(void);
 const char *rtw_last_error(void);
 int rtw_device_count(int *count);
 /* Frees every device resource the library owns: the sessions behind
- * rtw_threaded_render(_fast) and rtw_threaded_render_multi. Sessions the caller
+ * rtw_threaded_render(_fast) and rtw_threaded_render_multi, and the scratch of the
+ * device output stage (rtw_quantise_device, rtw_format_ppm_device). Sessions the caller
  * created with rtw_session_create stay the caller's. The next one-shot call
  * re-creates what it needs. Not to be called while another thread renders. */
 int rtw_shutdown(void);
@@ -323,6 +324,50 @@ const char *rtw_group_note(rtw_group *g);
 /* 1 if RCCL (librccl.so.1 with ncclCommInitAll/ncclGather) can be loaded, else 0 with
  * the reason in why[0..cap) (nullable). Needs no GPU. */
 int rtw_rccl_available(char *why, size_t cap);
+
+/* ---- the output stage on the device ----
+ * gamma_correct + quantise + Color::wire_full_file (color.rs:196-247) for a frame that
+ * lives in HBM (rtw_session_render(_fast), rtw_group_render(_fast)): hand-written HIP,
+ * no pow on the device. rgb_device: height*width*3 f64 (is_f32 = 0) or f32 (is_f32 != 0:
+ * widened to f64 exactly, then the same path) on `device`; `height` is the number of
+ * rows in the buffer, so a shard's tile works as well as a whole frame. The RGB8 image
+ * and the text are byte-identical to rtw_format_ppm's for EVERY input. A channel > 1
+ * (+inf included; also -inf, whose pow is +inf) is *wide*: its text can exceed "255"
+ * and needs pow, so it is stored as 255 in the RGB8 image and counted. Scratch lives in a per-device context the
+ * library owns (rtw_shutdown frees it); calls on one device are serialised, and ordered
+ * on the device across streams. Every call restores the caller's current HIP device.
+ * hip_stream: a hipStream_t of `device` (NULL = the null stream). */
+
+/* RGB8 (height*width*3 bytes, row-major) into rgb8_device. wide == NULL: asynchronous,
+ * enqueued on hip_stream. wide != NULL: waits, and *wide = the number of wide channels.
+ * A zero-sized image launches nothing. */
+int rtw_quantise_device(int device, const void *rgb_device, int is_f32, uint32_t width,
+                        uint32_t height, uint8_t *rgb8_device, void *hip_stream, uint64_t *wide);
+/* The same into a host buffer (blocking): quantised into the context's own RGB8 image
+ * and downloaded, 1/8 of the f64 frame's bytes. wide is nullable. */
+int rtw_quantise_host(int device, const void *rgb_device, int is_f32, uint32_t width,
+                      uint32_t height, uint8_t *rgb8_host, void *hip_stream, uint64_t *wide);
+/* rtw_format_ppm for a device frame (blocking). Returns the byte count; writes buf
+ * (host) only if buf != NULL and cap suffices. Three kernels on hip_stream (quantise +
+ * per-tile text sizes, scan of the tile offsets, text emit), then the text alone is
+ * downloaded. If any channel is wide the frame is downloaded instead and the host
+ * writer's bytes are returned: identical to rtw_format_ppm either way. *wide (nullable)
+ * = the number of wide channels, i.e. which path ran. A zero-sized image behaves as
+ * rtw_format_ppm does and launches nothing. */
+int64_t rtw_format_ppm_device(int device, const void *rgb_device, int is_f32, uint32_t width,
+                              uint32_t height, void *hip_stream, char *buf, uint64_t cap,
+                              uint64_t *wide);
+/* The last rtw_format_ppm_device of `device`: kernel times from HIP events on its
+ * stream, and what it produced. */
+typedef struct rtw_ppm_stats {
+    double quantise_ms, scan_ms, emit_ms; /* the three kernels                          */
+    double download_ms;                   /* host wall time of the text (or, on the wide
+                                             fallback, framebuffer) download            */
+    uint64_t tiles;                       /* text tiles (4096 channels each)            */
+    uint64_t text_bytes;                  /* bytes of the device text, header included  */
+    uint64_t wide;                        /* wide channels (non-zero: host fallback ran) */
+} rtw_ppm_stats;
+int rtw_ppm_device_stats(int device, rtw_ppm_stats *out);
 
 /* ---- device probes (tests) ---- */
 /* Device jump-ahead seeds (the kernel's own code path) for a pixel range. */

@@ -88,6 +88,15 @@ class GroupInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("_")}
 
 
+class PpmStats(C.Structure):
+    _fields_ = [("quantise_ms", C.c_double), ("scan_ms", C.c_double), ("emit_ms", C.c_double),
+                ("download_ms", C.c_double), ("tiles", C.c_uint64), ("text_bytes", C.c_uint64),
+                ("wide", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 GATHER_NAMES = {0: "none", 1: "copy", 2: "rccl"}
 FALLBACK_NAMES = {0: "none", 1: "rccl_unloadable", 2: "comm_init_failed"}
 GROUP_COPY_GATHER = 1
@@ -157,6 +166,13 @@ SIGNATURES = {
                                           C.c_void_p, C.c_void_p]),
     "rtw_session_stats": (C.c_int, [C.c_void_p, _P(Stats)]),
     "rtw_session_diag": (C.c_int, [C.c_void_p, _P(C.c_uint32), C.c_uint64]),
+    "rtw_quantise_device": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p,
+                                      C.c_void_p, _P(C.c_uint64)]),
+    "rtw_quantise_host": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p,
+                                    C.c_void_p, _P(C.c_uint64)]),
+    "rtw_format_ppm_device": (C.c_int64, [C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32,
+                                          C.c_void_p, C.c_char_p, C.c_uint64, _P(C.c_uint64)]),
+    "rtw_ppm_device_stats": (C.c_int, [C.c_int, _P(PpmStats)]),
     "rtw_probe_device_seeds": (C.c_int, [C.c_int, U128, C.c_uint64, C.c_uint64, _P(U128)]),
     "rtw_probe_f64_ops": (C.c_int, [C.c_int, _P(C.c_double), _P(C.c_double), C.c_uint64,
                                     _P(C.c_double), _P(C.c_double)]),

@@ -275,6 +275,51 @@ def write_ppm(path: str, fb: np.ndarray):
                             fb.shape[1], fb.shape[0]))
 
 
+def quantise_device(ptr: int, shape, fast: bool = False, device: int = 0, stream: int = 0,
+                    out_dev_ptr: int | None = None):
+    """rtw_quantise_device / rtw_quantise_host: the frame at device pointer `ptr` (shape
+    (rows, W[, 3]); f64, or f32 with fast=True) as the 8-bit image the PPM's numbers
+    are, made on the GPU. Returns (rows x W x 3 uint8 numpy array, wide), or, when
+    `out_dev_ptr` (a device buffer of rows*W*3 bytes) is given, writes there and returns
+    (None, wide). wide = channels above 1, stored as 255. Blocking. `stream`: a
+    hipStream_t handle of `device` (0 = the null stream)."""
+    h, w = int(shape[0]), int(shape[1])
+    wide = C.c_uint64()
+    if out_dev_ptr is not None:
+        check(lib.rtw_quantise_device(device, C.c_void_p(ptr), int(fast), w, h, C.c_void_p(out_dev_ptr),
+                                      C.c_void_p(stream or None), C.byref(wide)))
+        return None, wide.value
+    out = np.zeros((h, w, 3), dtype=np.uint8)
+    check(lib.rtw_quantise_host(device, C.c_void_p(ptr), int(fast), w, h, C.c_void_p(out.ctypes.data),
+                                C.c_void_p(stream or None), C.byref(wide)))
+    return out, wide.value
+
+
+def format_ppm_device(ptr: int, shape, fast: bool = False, device: int = 0, stream: int = 0):
+    """rtw_format_ppm_device: the reference's PPM file of the frame at device pointer
+    `ptr`, formatted on the GPU; only the text is downloaded. Returns (bytes, wide):
+    the bytes equal format_ppm of the downloaded frame for every input (wide != 0: a
+    channel above 1 sent the call through the host writer)."""
+    h, w = int(shape[0]), int(shape[1])
+    wide = C.c_uint64()
+    cap = 12 * w * h + 64  # enough unless a channel is wide
+    buf = C.create_string_buffer(cap)
+    n = check(lib.rtw_format_ppm_device(device, C.c_void_p(ptr), int(fast), w, h, C.c_void_p(stream or None),
+                                        buf, cap, C.byref(wide)))
+    if n > cap:
+        buf = C.create_string_buffer(n)
+        check(lib.rtw_format_ppm_device(device, C.c_void_p(ptr), int(fast), w, h, C.c_void_p(stream or None),
+                                        buf, n, C.byref(wide)))
+    return C.string_at(buf, n), wide.value
+
+
+def ppm_device_stats(device: int = 0) -> dict:
+    """Kernel times (HIP events) and sizes of the last format_ppm_device on `device`."""
+    st = capi.PpmStats()
+    check(lib.rtw_ppm_device_stats(device, C.byref(st)))
+    return st.as_dict()
+
+
 def xorshift_next_int(seed: int, n: int):
     out = (capi.U128 * max(1, n))()
     check(lib.rtw_xorshift_next_int(capi.U128.of(seed), n, out))

@@ -7,8 +7,10 @@
 // --scene (the other builders of mod.rs), --out, --mode parity|fast (fast: the
 // f32 statistical mode), --gpus N|LIST (N: the first N devices; LIST: comma-
 // separated device indices, repeats allowed; default: every visible device -- the
-// reference's pool takes every core, camera.rs:253). --preview is accepted and
-// ignored: the winit preview window (application/mod.rs) is out of scope.
+// reference's pool takes every core, camera.rs:253), --device-ppm (a one-device
+// render whose frame stays in HBM: the file's text is made there, rtw_format_ppm_device,
+// and is the same file byte for byte). --preview is accepted and ignored: the winit
+// preview window (application/mod.rs) is out of scope.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -27,7 +29,8 @@ struct Config {  // main.rs:13-29
     unsigned __int128 seed = 0;
     bool seed_set = false;
     bool fast = false;
-    std::vector<int> devices;  // empty: every visible device
+    bool device_ppm = false;
+    std::vector<int> devices;  // empty: every visible device (--device-ppm: device 0)
 };
 
 bool parse_u32(const char *s, uint32_t &v);
@@ -119,6 +122,7 @@ Config parse_args(int argc, char **argv) {
                 std::exit(1);
             }
         }
+        else if (a == "--device-ppm") c.device_ppm = true;
         else if (a == "--help") {
             std::printf("Use the application like this:\n");
             std::printf("\t-h --height\t:\tSet the height of the image\n");
@@ -131,8 +135,14 @@ Config parse_args(int argc, char **argv) {
             std::printf("\t--out PATH\t:\tOutput PPM (reference: img.ppm)\n");
             std::printf("\t--mode M\t:\tparity (f64, bit-exact; default) | fast (f32, statistical)\n");
             std::printf("\t--gpus N|LIST\t:\tthe first N GPUs, or device indices 0,1,.. (default: every GPU)\n");
+            std::printf("\t--device-ppm\t:\tone GPU; the frame stays in HBM and the PPM text is made there\n");
             std::exit(0);
         }
+    }
+    if (c.device_ppm && c.devices.size() > 1) {  // the frame of a multi-device render is gathered on the host
+        std::fprintf(stderr, "--device-ppm needs a one-device render: --gpus selects %zu devices\n",
+                     c.devices.size());
+        std::exit(1);
     }
     if (!c.seed_set)  // XorShift::default(): milliseconds since the Unix epoch
         c.seed = static_cast<unsigned long long>(
@@ -165,7 +175,16 @@ int main(int argc, char **argv) {
             b.cam.width(), b.cam.height(), cfg.sample_sqrt * cfg.sample_sqrt, b.cam.d.max_depth);
         rtw_stats st{};
         const auto t0 = std::chrono::steady_clock::now();
-        if (cfg.fast) {
+        if (cfg.device_ppm) {
+            uint64_t wide = 0;
+            const std::string text =
+                rtw::render_ppm_device(b.cam, *b.world, cfg.sample_sqrt, seed, cfg.fast,
+                                       cfg.devices.empty() ? 0 : cfg.devices[0], &st, &wide);
+            FILE *f = std::fopen(cfg.out.c_str(), "wb");
+            if (!f) throw rtw::Error(RTW_E_ARG, "cannot create " + cfg.out);
+            const bool short_write = std::fwrite(text.data(), 1, text.size(), f) != text.size();
+            if (std::fclose(f) != 0 || short_write) throw rtw::Error(RTW_E_ARG, "short write");
+        } else if (cfg.fast) {
             rtw::FlatScene flat;
             b.world->flatten(flat);
             std::vector<float> f32(static_cast<size_t>(b.cam.width()) * b.cam.height() * 3);

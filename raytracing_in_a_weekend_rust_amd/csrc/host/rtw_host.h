@@ -174,4 +174,20 @@ std::string format_ppm(const double *rgb, uint32_t w, uint32_t h);
 // the same text as the header followed by row-block chunks (no concatenation)
 std::vector<std::string> format_ppm_parts(const double *rgb, uint32_t w, uint32_t h);
 
+// The gamma table as the device encoder reads it (rtw_ppm.hip; built once per process
+// from the host writer's own thresholds): t[0] = 0, t[k] = bits of T_k, t[256] = bits
+// of 1.0; near[k][d + kNear] = the quantised value of the double with bits t[k] + d.
+struct GammaDeviceTable {
+    static constexpr uint64_t kNear = 64;
+    uint64_t t[257];
+    uint8_t near[256][2 * kNear];
+};
+const GammaDeviceTable &gamma_device_table();
+
+// rtw_cli --device-ppm: one-device render (parity or f32 fast mode) left in HBM and
+// encoded there by rtw_format_ppm_device; returns the file's bytes. Throws on error.
+std::string render_ppm_device(const Camera &cam, const Scene &world, uint32_t samples_sqrt,
+                              rtw_u128 seed, bool fast, int device, rtw_stats *stats,
+                              uint64_t *wide);
+
 }  // namespace rtw

@@ -45,6 +45,7 @@
 #include "rtw_capi.h"
 #include "rtw_fast.h"
 #include "rtw_numeric.h"
+#include "rtw_ppm.h"
 #include "host/rtw_host.h"
 #include "host/rtw_internal.h"
 
@@ -3592,6 +3593,7 @@ int rtw_shutdown(void) {
     g_one = nullptr;
     for (auto *s : g_multi) rtw_session_destroy(s);
     g_multi.clear();
+    rtw::ppm_shutdown();  // the device output stage's per-device contexts (rtw_ppm.hip)
     return RTW_OK;
 }
 
