@@ -45,7 +45,13 @@ $(OUT)/rtw_group.o: $(SRC)/rtw_group.hip include/rtw_capi.h $(SRC)/host/rtw_inte
 
 # the output stage on the device (RGB8 + P3 text). Integer and byte work only; packed
 # f32 instructions are kept out of its code object.
-$(OUT)/rtw_ppm.o: $(SRC)/rtw_ppm.hip $(SRC)/rtw_ppm.h include/rtw_capi.h $(SRC)/host/rtw_host.h $(SRC)/host/rtw_internal.h
+$(OUT)/rtw_ppm.o: $(SRC)/rtw_ppm.hip $(SRC)/rtw_ppm.h $(SRC)/rtw_png.h include/rtw_capi.h $(SRC)/host/rtw_host.h $(SRC)/host/rtw_internal.h
+	@mkdir -p $(OUT)
+	$(HIPCC) $(HIPFLAGS) -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
+
+# the PNG encoder on the device (filters, RLE tokens, dynamic Huffman, CRC-32): integer
+# and byte work only, built like the stage above
+$(OUT)/rtw_png.o: $(SRC)/rtw_png.hip $(SRC)/rtw_png.h include/rtw_capi.h $(SRC)/host/rtw_host.h $(SRC)/host/rtw_internal.h
 	@mkdir -p $(OUT)
 	$(HIPCC) $(HIPFLAGS) -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
 
@@ -78,7 +84,7 @@ $(OUT)/rtw_host.o: $(SRC)/host/rtw_host.cpp include/rtw_capi.h $(SRC)/host/rtw_h
 	@mkdir -p $(OUT)
 	$(CXX) $(CXXFLAGS) -I$(OUT) -c $< -o $@
 
-$(OUT)/librtw.so: $(OUT)/rtw_render.o $(OUT)/rtw_fast.o $(OUT)/rtw_group.o $(OUT)/rtw_ppm.o $(OUT)/rtw_host.o $(OUT)/rtw_accel_build.o
+$(OUT)/librtw.so: $(OUT)/rtw_render.o $(OUT)/rtw_fast.o $(OUT)/rtw_group.o $(OUT)/rtw_ppm.o $(OUT)/rtw_png.o $(OUT)/rtw_host.o $(OUT)/rtw_accel_build.o
 	$(HIPCC) $(ARCHFLAGS) -shared -fPIC -o $@ $^ -Wl,-soname,librtw.so -lpthread -ldl
 
 $(OUT)/rtw_cli: $(SRC)/host/rtw_cli.cpp $(OUT)/librtw.so
@@ -95,7 +101,7 @@ $(OUT)/rtw_render_stamps.o: $(SRC)/rtw_render.hip include/rtw_capi.h $(SRC)/host
 # library must not report the default build's id)
 $(OUT)/rtw_host_stamps.o: $(SRC)/host/rtw_host.cpp include/rtw_capi.h $(SRC)/host/rtw_host.h $(SRC)/host/rtw_internal.h $(OUT)/rtw_build_id.h
 	$(CXX) $(CXXFLAGS) -I$(OUT) '-DRTW_BUILD_VARIANT="+stamps"' -c $< -o $@
-$(OUT)/librtw_stamps.so: $(OUT)/rtw_render_stamps.o $(OUT)/rtw_fast.o $(OUT)/rtw_group.o $(OUT)/rtw_ppm.o $(OUT)/rtw_host_stamps.o $(OUT)/rtw_accel_build.o
+$(OUT)/librtw_stamps.so: $(OUT)/rtw_render_stamps.o $(OUT)/rtw_fast.o $(OUT)/rtw_group.o $(OUT)/rtw_ppm.o $(OUT)/rtw_png.o $(OUT)/rtw_host_stamps.o $(OUT)/rtw_accel_build.o
 	$(HIPCC) $(ARCHFLAGS) -shared -fPIC -o $@ $^ -Wl,-soname,librtw_stamps.so -lpthread
 
 RENDER_DEPS := $(SRC)/rtw_render.hip $(SRC)/rtw_fast.h $(SRC)/rtw_accel.h $(SRC)/rtw_numeric.h $(SRC)/rtw_ppm.h include/rtw_capi.h $(SRC)/host/rtw_host.h $(SRC)/host/rtw_internal.h

@@ -369,6 +369,42 @@ typedef struct rtw_ppm_stats {
 } rtw_ppm_stats;
 int rtw_ppm_device_stats(int device, rtw_ppm_stats *out);
 
+/* ---- PNG on the device ----
+ * A complete PNG file (signature, IHDR: 8-bit RGB, no interlace; one IDAT holding one
+ * zlib stream; IEND) made in HBM by hand-written HIP and downloaded once. The filtered
+ * stream, height * (1 + 3 * width) bytes, is cut into tiles of 2048 bytes; a workgroup
+ * encodes a tile as a dynamic-Huffman deflate block of literals and distance-1 matches
+ * (zlib's Z_RLE), or stored when that is not larger. filter: 0 None, 1 Sub, 2 Up for every
+ * row, or -1: per row the one with the smallest sum of |signed residual| (ties to the
+ * lower type). Both calls block, return the file's byte count and write buf (host) only
+ * if buf != NULL and cap suffices; height * (1 + 3 * width) * (1 + 5 / 2048) + 100 always
+ * does. Errors, found before any device work: width or height 0 is RTW_E_EMPTY_IMAGE,
+ * a filter outside -1..2 RTW_E_ARG, an image whose stream could pass 2^31 - 1 bytes
+ * (one IDAT) RTW_E_UNSUPPORTED. Scratch, serialisation, stream order and the caller's
+ * device are handled as for the stage above; rtw_shutdown frees the scratch. */
+
+/* From a frame (height*width*3 f64, or f32 with is_f32 != 0) on `device`: quantised on
+ * hip_stream by rtw_quantise_device into the encoder's own RGB8 image (a channel above
+ * 1 is 255, as an 8-bit PNG wants), then encoded. */
+int64_t rtw_png_device(int device, const void *rgb_device, int is_f32, uint32_t width,
+                       uint32_t height, int filter, void *hip_stream, char *buf, uint64_t cap);
+/* From an RGB8 image (height*width*3 bytes, row-major) on `device`. */
+int64_t rtw_png_rgb8_device(int device, const uint8_t *rgb8_device, uint32_t width,
+                            uint32_t height, int filter, void *hip_stream, char *buf,
+                            uint64_t cap);
+/* The last PNG call of `device`: kernel times from HIP events on its stream, and what
+ * it produced. */
+typedef struct rtw_png_stats {
+    double quantise_ms, filter_ms, plan_ms, scan_ms, emit_ms, finish_ms; /* the stages   */
+    double download_ms;      /* host wall time of the file's download (0: buf not written) */
+    uint64_t tiles;          /* deflate tiles (2048 filtered bytes each)                  */
+    uint64_t stored_tiles;   /* of them, emitted as stored blocks                         */
+    uint64_t rows_none, rows_sub, rows_up; /* rows per filter type                        */
+    uint64_t filtered_bytes; /* height * (1 + 3 * width)                                  */
+    uint64_t png_bytes;      /* the file                                                  */
+} rtw_png_stats;
+int rtw_png_device_stats(int device, rtw_png_stats *out);
+
 /* ---- device probes (tests) ---- */
 /* Device jump-ahead seeds (the kernel's own code path) for a pixel range. */
 int rtw_probe_device_seeds(int device, rtw_u128 seed, uint64_t first_pixel, uint64_t count,

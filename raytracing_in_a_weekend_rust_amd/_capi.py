@@ -97,6 +97,16 @@ class PpmStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class PngStats(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("quantise_ms", "filter_ms", "plan_ms", "scan_ms", "emit_ms",
+                                          "finish_ms", "download_ms")] + \
+               [(k, C.c_uint64) for k in ("tiles", "stored_tiles", "rows_none", "rows_sub", "rows_up",
+                                          "filtered_bytes", "png_bytes")]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 GATHER_NAMES = {0: "none", 1: "copy", 2: "rccl"}
 FALLBACK_NAMES = {0: "none", 1: "rccl_unloadable", 2: "comm_init_failed"}
 GROUP_COPY_GATHER = 1
@@ -173,6 +183,11 @@ SIGNATURES = {
     "rtw_format_ppm_device": (C.c_int64, [C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32,
                                           C.c_void_p, C.c_char_p, C.c_uint64, _P(C.c_uint64)]),
     "rtw_ppm_device_stats": (C.c_int, [C.c_int, _P(PpmStats)]),
+    "rtw_png_device": (C.c_int64, [C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p,
+                                   C.c_char_p, C.c_uint64]),
+    "rtw_png_rgb8_device": (C.c_int64, [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p,
+                                        C.c_char_p, C.c_uint64]),
+    "rtw_png_device_stats": (C.c_int, [C.c_int, _P(PngStats)]),
     "rtw_probe_device_seeds": (C.c_int, [C.c_int, U128, C.c_uint64, C.c_uint64, _P(U128)]),
     "rtw_probe_f64_ops": (C.c_int, [C.c_int, _P(C.c_double), _P(C.c_double), C.c_uint64,
                                     _P(C.c_double), _P(C.c_double)]),

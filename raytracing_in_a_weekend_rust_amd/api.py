@@ -320,6 +320,36 @@ def ppm_device_stats(device: int = 0) -> dict:
     return st.as_dict()
 
 
+PNG_TILE = 2048  # filtered bytes per deflate tile (rtw_png.h kPngTile)
+
+
+def png_device(dev_ptr: int, shape, fast: bool = False, rgb8: bool = False, filter: int | None = None,
+               stream: int | None = None, device: int = 0) -> bytes:
+    """rtw_png_device / rtw_png_rgb8_device: the PNG file (8-bit RGB) of the frame at
+    device pointer `dev_ptr` (shape (rows, W[, 3]); f64, f32 with fast=True, or the
+    RGB8 image itself with rgb8=True), filtered, deflated and checksummed on the GPU;
+    only the file is downloaded. filter: None = per-row choice among None/Sub/Up, or
+    0, 1, 2 to force one. Blocking. png_device_stats() describes the call."""
+    h, w = int(shape[0]), int(shape[1])
+    f = -1 if filter is None else int(filter)
+    filtered = h * (1 + 3 * w)
+    cap = filtered + 5 * (filtered // PNG_TILE + 1) + 100  # a tile is never larger than stored
+    buf = C.create_string_buffer(cap)
+    st = C.c_void_p(stream or None)
+    if rgb8:
+        n = check(lib.rtw_png_rgb8_device(device, C.c_void_p(dev_ptr), w, h, f, st, buf, cap))
+    else:
+        n = check(lib.rtw_png_device(device, C.c_void_p(dev_ptr), int(fast), w, h, f, st, buf, cap))
+    return C.string_at(buf, n)
+
+
+def png_device_stats(device: int = 0) -> dict:
+    """Kernel times (HIP events), tiles, rows per filter and sizes of the last png_device on `device`."""
+    st = capi.PngStats()
+    check(lib.rtw_png_device_stats(device, C.byref(st)))
+    return st.as_dict()
+
+
 def xorshift_next_int(seed: int, n: int):
     out = (capi.U128 * max(1, n))()
     check(lib.rtw_xorshift_next_int(capi.U128.of(seed), n, out))

@@ -9,7 +9,9 @@
 // separated device indices, repeats allowed; default: every visible device -- the
 // reference's pool takes every core, camera.rs:253), --device-ppm (a one-device
 // render whose frame stays in HBM: the file's text is made there, rtw_format_ppm_device,
-// and is the same file byte for byte). --preview is accepted and ignored: the winit
+// and is the same file byte for byte), --png (a one-device render encoded to a PNG file on
+// the device, rtw_png_device; written to img.png unless --out names a file; takes
+// precedence over the PPM). --preview is accepted and ignored: the winit
 // preview window (application/mod.rs) is out of scope.
 #include <chrono>
 #include <cstdio>
@@ -30,6 +32,7 @@ struct Config {  // main.rs:13-29
     bool seed_set = false;
     bool fast = false;
     bool device_ppm = false;
+    bool png = false, out_set = false;
     std::vector<int> devices;  // empty: every visible device (--device-ppm: device 0)
 };
 
@@ -108,7 +111,7 @@ Config parse_args(int argc, char **argv) {
             c.seed_set = true;
         }
         else if (a == "--scene" && next) c.scene = next;
-        else if (a == "--out" && next) c.out = next;
+        else if (a == "--out" && next) c.out = next, c.out_set = true;
         else if (a == "--mode" && next) {
             if (std::strcmp(next, "fast") && std::strcmp(next, "parity")) {
                 std::fprintf(stderr, "Usage: --mode parity|fast\n");
@@ -123,6 +126,7 @@ Config parse_args(int argc, char **argv) {
             }
         }
         else if (a == "--device-ppm") c.device_ppm = true;
+        else if (a == "--png") c.png = true;
         else if (a == "--help") {
             std::printf("Use the application like this:\n");
             std::printf("\t-h --height\t:\tSet the height of the image\n");
@@ -132,18 +136,20 @@ Config parse_args(int argc, char **argv) {
             std::printf("\t--depth -d\t:\tMax bounce depth (reference: 10)\n");
             std::printf("\t--seed N\t:\tXorShift seed (decimal) for scene and render (reference: wall-clock ms)\n");
             std::printf("\t--scene NAME\t:\tcomplex | simple | threads | super_simple | three_lambertian\n");
-            std::printf("\t--out PATH\t:\tOutput PPM (reference: img.ppm)\n");
+            std::printf("\t--out PATH\t:\tOutput file (reference: img.ppm; with --png: img.png)\n");
             std::printf("\t--mode M\t:\tparity (f64, bit-exact; default) | fast (f32, statistical)\n");
             std::printf("\t--gpus N|LIST\t:\tthe first N GPUs, or device indices 0,1,.. (default: every GPU)\n");
             std::printf("\t--device-ppm\t:\tone GPU; the frame stays in HBM and the PPM text is made there\n");
+            std::printf("\t--png\t\t:\tone GPU; the frame is encoded to a PNG file there; takes precedence over the PPM\n");
             std::exit(0);
         }
     }
-    if (c.device_ppm && c.devices.size() > 1) {  // the frame of a multi-device render is gathered on the host
-        std::fprintf(stderr, "--device-ppm needs a one-device render: --gpus selects %zu devices\n",
-                     c.devices.size());
+    if ((c.device_ppm || c.png) && c.devices.size() > 1) {  // the frame of a multi-device render is gathered on the host
+        std::fprintf(stderr, "%s needs a one-device render: --gpus selects %zu devices\n",
+                     c.png ? "--png" : "--device-ppm", c.devices.size());
         std::exit(1);
     }
+    if (c.png && !c.out_set) c.out = "img.png";
     if (!c.seed_set)  // XorShift::default(): milliseconds since the Unix epoch
         c.seed = static_cast<unsigned long long>(
             std::chrono::duration_cast<std::chrono::milliseconds>(
@@ -175,11 +181,12 @@ int main(int argc, char **argv) {
             b.cam.width(), b.cam.height(), cfg.sample_sqrt * cfg.sample_sqrt, b.cam.d.max_depth);
         rtw_stats st{};
         const auto t0 = std::chrono::steady_clock::now();
-        if (cfg.device_ppm) {
+        if (cfg.png || cfg.device_ppm) {
             uint64_t wide = 0;
+            const int device = cfg.devices.empty() ? 0 : cfg.devices[0];
             const std::string text =
-                rtw::render_ppm_device(b.cam, *b.world, cfg.sample_sqrt, seed, cfg.fast,
-                                       cfg.devices.empty() ? 0 : cfg.devices[0], &st, &wide);
+                cfg.png ? rtw::render_png_device(b.cam, *b.world, cfg.sample_sqrt, seed, cfg.fast, device, -1, &st)
+                        : rtw::render_ppm_device(b.cam, *b.world, cfg.sample_sqrt, seed, cfg.fast, device, &st, &wide);
             FILE *f = std::fopen(cfg.out.c_str(), "wb");
             if (!f) throw rtw::Error(RTW_E_ARG, "cannot create " + cfg.out);
             const bool short_write = std::fwrite(text.data(), 1, text.size(), f) != text.size();

@@ -189,5 +189,9 @@ const GammaDeviceTable &gamma_device_table();
 std::string render_ppm_device(const Camera &cam, const Scene &world, uint32_t samples_sqrt,
                               rtw_u128 seed, bool fast, int device, rtw_stats *stats,
                               uint64_t *wide);
+// rtw_cli --png: the same render encoded by rtw_png_device (rtw_png.hip); returns the
+// PNG file's bytes. filter: -1 adaptive, 0..2 forced. Throws on error.
+std::string render_png_device(const Camera &cam, const Scene &world, uint32_t samples_sqrt,
+                              rtw_u128 seed, bool fast, int device, int filter, rtw_stats *stats);
 
 }  // namespace rtw

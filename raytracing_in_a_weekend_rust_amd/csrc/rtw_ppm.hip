@@ -32,6 +32,7 @@
 #include "rtw_capi.h"
 #include "rtw_host.h"
 #include "rtw_internal.h"
+#include "rtw_png.h"
 #include "rtw_ppm.h"
 
 namespace {
@@ -504,6 +505,7 @@ int64_t format_device(int device, const void *rgb, int is_f32, uint32_t width, u
 namespace rtw {
 
 void ppm_shutdown() {
+    png_shutdown();  // the PNG encoder's contexts (rtw_png.hip) go with this stage's
     DeviceGuard guard;
     std::lock_guard<std::mutex> lock(g_mu);
     for (auto &kv : g_ctx) delete kv.second;
