@@ -34,9 +34,15 @@ $(OUT)/rtw_render.o: $(SRC)/rtw_render.hip $(SRC)/rtw_fast.h $(SRC)/rtw_accel.h 
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # f32 fast mode: FMA contraction allowed (its own file, its own flags)
-$(OUT)/rtw_fast.o: $(SRC)/rtw_fast.hip $(SRC)/rtw_fast.h $(SRC)/rtw_accel.h include/rtw_capi.h
+$(OUT)/rtw_fast.o: $(SRC)/rtw_fast.hip $(SRC)/rtw_fast_dev.h $(SRC)/rtw_fast.h $(SRC)/rtw_accel.h include/rtw_capi.h
 	@mkdir -p $(OUT)
 	$(HIPCC) $(filter-out -ffp-contract=off,$(HIPFLAGS)) -ffp-contract=fast -c $< -o $@
+
+# progressive fast mode: the accumulate and resolve kernels, the flags of the file above
+# (a sample must have the one-shot kernel's bits) without packed f32 instructions
+$(OUT)/rtw_fast_acc.o: $(SRC)/rtw_fast_acc.hip $(SRC)/rtw_fast_dev.h $(SRC)/rtw_fast.h $(SRC)/rtw_accel.h include/rtw_capi.h
+	@mkdir -p $(OUT)
+	$(HIPCC) $(filter-out -ffp-contract=off,$(HIPFLAGS)) -ffp-contract=fast -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
 
 # multi-GPU groups (RCCL gather, opened with dlopen at first use)
 $(OUT)/rtw_group.o: $(SRC)/rtw_group.hip include/rtw_capi.h $(SRC)/host/rtw_internal.h
@@ -84,7 +90,7 @@ $(OUT)/rtw_host.o: $(SRC)/host/rtw_host.cpp include/rtw_capi.h $(SRC)/host/rtw_h
 	@mkdir -p $(OUT)
 	$(CXX) $(CXXFLAGS) -I$(OUT) -c $< -o $@
 
-$(OUT)/librtw.so: $(OUT)/rtw_render.o $(OUT)/rtw_fast.o $(OUT)/rtw_group.o $(OUT)/rtw_ppm.o $(OUT)/rtw_png.o $(OUT)/rtw_host.o $(OUT)/rtw_accel_build.o
+$(OUT)/librtw.so: $(OUT)/rtw_render.o $(OUT)/rtw_fast.o $(OUT)/rtw_fast_acc.o $(OUT)/rtw_group.o $(OUT)/rtw_ppm.o $(OUT)/rtw_png.o $(OUT)/rtw_host.o $(OUT)/rtw_accel_build.o
 	$(HIPCC) $(ARCHFLAGS) -shared -fPIC -o $@ $^ -Wl,-soname,librtw.so -lpthread -ldl
 
 $(OUT)/rtw_cli: $(SRC)/host/rtw_cli.cpp $(OUT)/librtw.so
@@ -101,7 +107,7 @@ $(OUT)/rtw_render_stamps.o: $(SRC)/rtw_render.hip include/rtw_capi.h $(SRC)/host
 # library must not report the default build's id)
 $(OUT)/rtw_host_stamps.o: $(SRC)/host/rtw_host.cpp include/rtw_capi.h $(SRC)/host/rtw_host.h $(SRC)/host/rtw_internal.h $(OUT)/rtw_build_id.h
 	$(CXX) $(CXXFLAGS) -I$(OUT) '-DRTW_BUILD_VARIANT="+stamps"' -c $< -o $@
-$(OUT)/librtw_stamps.so: $(OUT)/rtw_render_stamps.o $(OUT)/rtw_fast.o $(OUT)/rtw_group.o $(OUT)/rtw_ppm.o $(OUT)/rtw_png.o $(OUT)/rtw_host_stamps.o $(OUT)/rtw_accel_build.o
+$(OUT)/librtw_stamps.so: $(OUT)/rtw_render_stamps.o $(OUT)/rtw_fast.o $(OUT)/rtw_fast_acc.o $(OUT)/rtw_group.o $(OUT)/rtw_ppm.o $(OUT)/rtw_png.o $(OUT)/rtw_host_stamps.o $(OUT)/rtw_accel_build.o
 	$(HIPCC) $(ARCHFLAGS) -shared -fPIC -o $@ $^ -Wl,-soname,librtw_stamps.so -lpthread
 
 RENDER_DEPS := $(SRC)/rtw_render.hip $(SRC)/rtw_fast.h $(SRC)/rtw_accel.h $(SRC)/rtw_numeric.h $(SRC)/rtw_ppm.h include/rtw_capi.h $(SRC)/host/rtw_host.h $(SRC)/host/rtw_internal.h

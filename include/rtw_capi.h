@@ -405,6 +405,47 @@ typedef struct rtw_png_stats {
 } rtw_png_stats;
 int rtw_png_device_stats(int device, rtw_png_stats *out);
 
+/* ---- progressive fast mode (ABI 7 additions) ----
+ * A fast-mode pixel is an exact, order-free sum of 32.32 fixed-point sample colours, each a
+ * function of (seed, global pixel, lattice sample k) alone. So the lattice may be traced in
+ * passes into a buffer of sums that the caller keeps, and looked at after every pass. */
+
+/* Adds lattice samples k_first + i*k_step (i < k_count) of every pixel of `shard` to
+ * acc_device: n_rows*W*3 u64 on the session's device, caller-owned, row-major like the
+ * f32 frame. Each channel is the sum of the samples' colours in 32.32 fixed point.
+ * Same camera, scene, seed mix, per-(pixel,k) streams, lattice positions and clamp
+ * (cmax from samples_sqrt^2, not from k_count) as rtw_session_render_fast. So accumulating
+ * every k of the lattice exactly once, in any split and order, into a zeroed buffer
+ * gives the sums of the one-shot render.
+ * Range: the buffer holds any number of accumulations while 2^32 * (sum of colours) < 2^63
+ * per channel; scenes whose colours stay in [0, 1] (the reference's) have room for 2^31
+ * samples per pixel.
+ * Asynchronous on hip_stream. Ordering, latch and rtw_session_stats as for
+ * rtw_session_render_fast (pixels, samples = pixels*k_count, segments, kernel_ms ...).
+ * Errors, found before any device work: a null acc_device, k_step == 0 with k_count > 1,
+ * or k_first + (k_count-1)*k_step >= samples_sqrt^2 (1 when samples_sqrt is 0) is
+ * RTW_E_ARG; rtw_session_render_fast's own checks apply. k_count == 0 launches nothing
+ * and succeeds. */
+int rtw_session_accumulate_fast(rtw_session *s, const rtw_camera *cam, uint32_t samples_sqrt,
+                                rtw_u128 seed, const rtw_shard *shard, uint32_t k_first,
+                                uint32_t k_step, uint32_t k_count,
+                                unsigned long long *acc_device, void *hip_stream);
+
+/* Resolves sums to images. Asynchronous on hip_stream. Either output may be NULL, not both.
+ * out_rgb_device: height*width*3 f32 = (float)((double)acc * 2^-32 / (double)n_samples),
+ *   the one-shot kernel's own expression, so a completed lattice is bit-identical to
+ *   rtw_session_render_fast. The gamma-corrected outputs need nothing new:
+ *   rtw_quantise_device, rtw_format_ppm_device and rtw_png_device take this frame.
+ * preview_rgba8_device: height*width*4 bytes (4-byte aligned) as the reference's
+ *   Application::draw fills its window frame: per channel ((double)mean_f32 * 255.) as u8
+ *   (Rust's saturating cast: truncation, NaN and negatives 0, above 255 -> 255), linear, no
+ *   gamma, A = 0xFF. One aligned 32-bit store per pixel.
+ * Errors: a null acc_device, both outputs null or n_samples == 0 is RTW_E_ARG; width or
+ * height 0 is RTW_E_EMPTY_IMAGE. */
+int rtw_resolve_fast(int device, const unsigned long long *acc_device, uint64_t n_samples,
+                     uint32_t width, uint32_t height, float *out_rgb_device,
+                     uint8_t *preview_rgba8_device, void *hip_stream);
+
 /* ---- device probes (tests) ---- */
 /* Device jump-ahead seeds (the kernel's own code path) for a pixel range. */
 int rtw_probe_device_seeds(int device, rtw_u128 seed, uint64_t first_pixel, uint64_t count,

@@ -174,6 +174,10 @@ SIGNATURES = {
                                      C.c_void_p, C.c_void_p]),
     "rtw_session_render_fast": (C.c_int, [C.c_void_p, _P(Camera), C.c_uint32, U128, _P(Shard),
                                           C.c_void_p, C.c_void_p]),
+    "rtw_session_accumulate_fast": (C.c_int, [C.c_void_p, _P(Camera), C.c_uint32, U128, _P(Shard),
+                                              C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "rtw_resolve_fast": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
     "rtw_session_stats": (C.c_int, [C.c_void_p, _P(Stats)]),
     "rtw_session_diag": (C.c_int, [C.c_void_p, _P(C.c_uint32), C.c_uint64]),
     "rtw_quantise_device": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p,

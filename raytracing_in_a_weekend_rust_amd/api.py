@@ -374,6 +374,15 @@ def device_count() -> int:
     return n.value
 
 
+def resolve_fast(acc_ptr: int, shape, n_samples: int, out_ptr: int = 0, preview_ptr: int = 0, device: int = 0,
+                 stream: int = 0):
+    """rtw_resolve_fast: (h, w, 3) u64 sums to the f32 mean frame at out_ptr and/or the
+    linear RGBA8 preview at preview_ptr (0: not wanted), asynchronously on `stream`."""
+    h, w = shape
+    check(lib.rtw_resolve_fast(device, C.c_void_p(acc_ptr), n_samples, w, h, C.c_void_p(out_ptr or None),
+                               C.c_void_p(preview_ptr or None), C.c_void_p(stream or 0)))
+
+
 class Session:
     """Device-resident rendering (rtw_session_*): the scene lives in HBM; renders
     are enqueued on a caller HIP stream into a caller device buffer."""
@@ -399,6 +408,37 @@ class Session:
         check(lib.rtw_session_render_fast(self.h, C.byref(cam), samples_sqrt, capi.U128.of(seed),
                                           C.byref(sh) if sh is not None else None,
                                           C.c_void_p(out_dev_ptr), C.c_void_p(stream or 0)))
+
+    def accumulate_fast(self, cam: capi.Camera, samples_sqrt: int, seed: int, acc_ptr: int, k_first: int = 0,
+                        k_step: int = 1, k_count: int | None = None, shard=None, stream: int = 0):
+        """Adds lattice samples k_first + i*k_step (i < k_count; default: up to the lattice's
+        end) of every pixel to the n_rows x W x 3 u64 fixed-point sums at acc_ptr."""
+        if k_count is None:
+            n = max(1, samples_sqrt * samples_sqrt)
+            k_count = (n - k_first + k_step - 1) // k_step if k_step and k_first < n else 1
+        sh = _shard(shard)
+        check(lib.rtw_session_accumulate_fast(self.h, C.byref(cam), samples_sqrt, capi.U128.of(seed),
+                                              C.byref(sh) if sh is not None else None, k_first, k_step,
+                                              k_count, C.c_void_p(acc_ptr), C.c_void_p(stream or 0)))
+
+    def progressive_fast(self, cam: capi.Camera, samples_sqrt: int, seed: int, passes: int):
+        """Renders the lattice in `passes` strided passes (pass p: k = p mod passes) and
+        yields (samples_done, frame_f32, preview_rgba8), torch tensors on the current
+        device, after each. The last frame is render_fast's, bit for bit."""
+        import torch
+        h, w = cam.img_height, cam.img_width
+        n = max(1, samples_sqrt * samples_sqrt)
+        acc = torch.zeros((h, w, 3), dtype=torch.int64, device="cuda")
+        frame = torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
+        preview = torch.empty((h, w, 4), dtype=torch.uint8, device="cuda")
+        st = torch.cuda.current_stream().cuda_stream
+        done = 0
+        for p in range(min(passes, n)):
+            self.accumulate_fast(cam, samples_sqrt, seed, acc.data_ptr(), p, passes, stream=st)
+            done += (n - p + passes - 1) // passes
+            resolve_fast(acc.data_ptr(), (h, w), done, frame.data_ptr(), preview.data_ptr(),
+                         acc.device.index, st)
+            yield done, frame, preview
 
     def stats(self) -> capi.Stats:
         st = capi.Stats()

@@ -11,8 +11,11 @@
 // render whose frame stays in HBM: the file's text is made there, rtw_format_ppm_device,
 // and is the same file byte for byte), --png (a one-device render encoded to a PNG file on
 // the device, rtw_png_device; written to img.png unless --out names a file; takes
-// precedence over the PPM). --preview is accepted and ignored: the winit
-// preview window (application/mod.rs) is out of scope.
+// precedence over the PPM), --passes N (fast mode, one device: the lattice in N strided
+// passes whose sums add up to the same file, each pass's kernel time printed) and
+// --preview-dir DIR (with it: the running mean after every pass as DIR/pass_%04u.png, the
+// headless stand-in for the reference's preview window). --preview is accepted and
+// ignored: the winit window itself (application/mod.rs) is out of scope.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -33,6 +36,8 @@ struct Config {  // main.rs:13-29
     bool fast = false;
     bool device_ppm = false;
     bool png = false, out_set = false;
+    uint32_t passes = 0;  // > 0: progressive fast mode
+    std::string preview_dir;
     std::vector<int> devices;  // empty: every visible device (--device-ppm: device 0)
 };
 
@@ -127,6 +132,8 @@ Config parse_args(int argc, char **argv) {
         }
         else if (a == "--device-ppm") c.device_ppm = true;
         else if (a == "--png") c.png = true;
+        else if (a == "--passes") need(c.passes, "--passes");
+        else if (a == "--preview-dir" && next) c.preview_dir = next;
         else if (a == "--help") {
             std::printf("Use the application like this:\n");
             std::printf("\t-h --height\t:\tSet the height of the image\n");
@@ -141,8 +148,15 @@ Config parse_args(int argc, char **argv) {
             std::printf("\t--gpus N|LIST\t:\tthe first N GPUs, or device indices 0,1,.. (default: every GPU)\n");
             std::printf("\t--device-ppm\t:\tone GPU; the frame stays in HBM and the PPM text is made there\n");
             std::printf("\t--png\t\t:\tone GPU; the frame is encoded to a PNG file there; takes precedence over the PPM\n");
+            std::printf("\t--passes N\t:\tfast mode, one GPU: render in N passes over the whole lattice (same file)\n");
+            std::printf("\t--preview-dir D\t:\twith --passes: the image so far after each pass as D/pass_NNNN.png\n");
             std::exit(0);
         }
+    }
+    if (!c.preview_dir.empty() && !c.passes) c.passes = 1;
+    if (c.passes && (!c.fast || c.device_ppm || c.devices.size() > 1)) {
+        std::fprintf(stderr, "--passes and --preview-dir need --mode fast on one device, without --device-ppm\n");
+        std::exit(1);
     }
     if ((c.device_ppm || c.png) && c.devices.size() > 1) {  // the frame of a multi-device render is gathered on the host
         std::fprintf(stderr, "%s needs a one-device render: --gpus selects %zu devices\n",
@@ -181,7 +195,23 @@ int main(int argc, char **argv) {
             b.cam.width(), b.cam.height(), cfg.sample_sqrt * cfg.sample_sqrt, b.cam.d.max_depth);
         rtw_stats st{};
         const auto t0 = std::chrono::steady_clock::now();
-        if (cfg.png || cfg.device_ppm) {
+        if (cfg.passes) {
+            std::vector<float> f32, ms;
+            const std::string png = rtw::render_progressive_device(b.cam, *b.world, cfg.sample_sqrt, seed,
+                                                                   cfg.devices.empty() ? 0 : cfg.devices[0], cfg.passes,
+                                                                   cfg.preview_dir, cfg.png, &f32, &ms, &st);
+            for (size_t p = 0; p < ms.size(); ++p) std::printf("pass %zu: kernel %.3f ms\n", p, ms[p]);
+            if (cfg.png) {
+                FILE *f = std::fopen(cfg.out.c_str(), "wb");
+                if (!f) throw rtw::Error(RTW_E_ARG, "cannot create " + cfg.out);
+                const bool short_write = std::fwrite(png.data(), 1, png.size(), f) != png.size();
+                if (std::fclose(f) != 0 || short_write) throw rtw::Error(RTW_E_ARG, "short write");
+            } else {
+                const std::vector<double> fb(f32.begin(), f32.end());
+                const int rc = rtw_write_ppm(cfg.out.c_str(), fb.data(), b.cam.width(), b.cam.height());
+                if (rc != RTW_OK) throw rtw::Error(rc, rtw_last_error());
+            }
+        } else if (cfg.png || cfg.device_ppm) {
             uint64_t wide = 0;
             const int device = cfg.devices.empty() ? 0 : cfg.devices[0];
             const std::string text =

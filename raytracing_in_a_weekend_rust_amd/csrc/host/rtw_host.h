@@ -193,5 +193,13 @@ std::string render_ppm_device(const Camera &cam, const Scene &world, uint32_t sa
 // PNG file's bytes. filter: -1 adaptive, 0..2 forced. Throws on error.
 std::string render_png_device(const Camera &cam, const Scene &world, uint32_t samples_sqrt,
                               rtw_u128 seed, bool fast, int device, int filter, rtw_stats *stats);
+// rtw_cli --mode fast --passes N: the lattice in N strided passes on one device
+// (rtw_session_accumulate_fast, rtw_resolve_fast). pass_ms gets each pass's kernel time.
+// preview_dir (not empty): the running mean after pass p as preview_dir/pass_%04u.png.
+// png: returns the final frame's PNG file; otherwise *frame gets the final f32 frame,
+// which is rtw_session_render_fast's bit for bit. Throws on error.
+std::string render_progressive_device(const Camera &cam, const Scene &world, uint32_t samples_sqrt, rtw_u128 seed,
+                                      int device, uint32_t passes, const std::string &preview_dir, bool png,
+                                      std::vector<float> *frame, std::vector<float> *pass_ms, rtw_stats *stats);
 
 }  // namespace rtw

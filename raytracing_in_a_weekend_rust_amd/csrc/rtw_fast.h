@@ -52,4 +52,31 @@ size_t lds_bytes(uint32_t n_sph, uint32_t n_node, uint32_t n_stack, bool *scene_
 // Enqueues the render (zeroes the cursor and counters first).
 hipError_t launch(const FastParams &P, int n_cu, hipStream_t st, bool scene_lds = true);
 
+// ---- progressive accumulation (rtw_fast_acc.hip)
+// Lattice samples k_first + i k_step (i < k_count) of every pixel of the shard, added
+// to the caller's 32.32 fixed-point sums. f.out is unused; f.n_off and f.cmax are the
+// whole lattice's, so a sample has the bits it has in the one-shot render.
+struct AccParams {
+    FastParams f;
+    uint32_t k_first, k_step, k_count;
+    uint32_t chunk;  // ring: pixels a wave claims per cursor atomic (set by launch_accumulate)
+    unsigned long long *acc;  // n_rows x W x 3 u64
+};
+
+// Below this k_count a lane owns a whole pixel (sums in registers); from it on, a wave
+// shares a ring of kAccRing pixels (sums in LDS), kAccRing * kAccLaneMax >= 2 x 64 lanes.
+constexpr uint32_t kAccLaneMax = 16;
+constexpr uint32_t kAccRing = 8;
+// two workgroups per CU with the ring sums (8 waves x kAccRing x 3 u64) beside them
+constexpr uint32_t kAccLdsCap = 80 * 1024 - (kBlock / 64) * kAccRing * 3 * 8;
+
+size_t acc_lds_bytes(uint32_t n_sph, uint32_t n_node, uint32_t n_stack, bool *scene_in_lds);
+
+// Enqueues the accumulation (zeroes the cursor and counters first); k_count = 0 launches nothing.
+hipError_t launch_accumulate(const AccParams &A, int n_cu, hipStream_t st, bool scene_lds = true);
+
+// Sums to the f32 mean frame and/or the linear RGBA8 preview (either may be null).
+hipError_t launch_resolve(const unsigned long long *acc, uint64_t n_samples, uint64_t n_pixels, float *out_rgb,
+                          uint32_t *preview_rgba8, hipStream_t st);
+
 }  // namespace rtw_fast

@@ -29,169 +29,10 @@
 
 #include <cstdlib>
 
-#include "rtw_accel.h"
-#include "rtw_capi.h"
+#include "rtw_fast_dev.h"
 
 namespace rtw_fast {
 namespace {
-
-constexpr uint32_t kWaves = kBlock / 64;
-constexpr uint32_t kRing = 4;
-constexpr uint32_t kFree = 0xffffffffu;
-
-struct Rng {
-    uint32_t a, b;
-};
-
-__device__ __forceinline__ uint64_t fmix64(uint64_t z) {  // SplitMix64's finaliser
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
-__device__ __forceinline__ Rng rng_for(uint64_t mix, uint64_t pix, uint32_t k) {
-    const uint64_t z = fmix64(fmix64(mix ^ (pix * 0x9e3779b97f4a7c15ull)) + k);
-    Rng r{static_cast<uint32_t>(z), static_cast<uint32_t>(z >> 32)};
-    if ((r.a | r.b) == 0u) r.a = 1u;
-    return r;
-}
-// xoroshiro64**
-__device__ __forceinline__ uint32_t rnext(Rng &r) {
-    const uint32_t s0 = r.a;
-    uint32_t s1 = r.b;
-    const uint32_t res = __builtin_rotateleft32(s0 * 0x9E3779BBu, 5) * 5u;
-    s1 ^= s0;
-    r.a = __builtin_rotateleft32(s0, 26) ^ s1 ^ (s1 << 9);
-    r.b = __builtin_rotateleft32(s1, 13);
-    return res;
-}
-// next_bound(-1, 1) (random.rs:54-59) on a 24-bit uniform; next_01 (40-52)
-__device__ __forceinline__ float rcoord(Rng &r) {
-    return fmaf(static_cast<float>(rnext(r) >> 8), 1.1920928955078125e-07f, -1.f);  // 2^-23
-}
-__device__ __forceinline__ float r01(Rng &r) {
-    return static_cast<float>(rnext(r) >> 8) * 5.9604644775390625e-08f;  // 2^-24
-}
-// random_unit_vec (vec3.rs:219-232) draws uniformly on the unit sphere by rejection;
-// fast mode draws the same distribution directly (z uniform in [-1, 1], azimuth
-// uniform: Archimedes), with no divergent retry loop. v_sin/v_cos take revolutions.
-__device__ __forceinline__ void unit_vec(Rng &r, float &x, float &y, float &z) {
-    z = rcoord(r);
-    const float t = r01(r);
-    const float s = __builtin_sqrtf(fmaxf(fmaf(-z, z, 1.f), 0.f));
-    x = s * __builtin_amdgcn_cosf(t), y = s * __builtin_amdgcn_sinf(t);
-}
-// random_vec_in_unit_disk (vec3.rs:270-277), uniform in the open disk, directly
-__device__ __forceinline__ void disk_vec(Rng &r, float &x, float &y) {
-    const float rad = __builtin_sqrtf(r01(r)), t = r01(r);
-    x = rad * __builtin_amdgcn_cosf(t), y = rad * __builtin_amdgcn_sinf(t);
-}
-
-// A segment: origin, unit direction, t_min = 0.01 |d| in distance units.
-struct Seg {
-    float ox, oy, oz, ex, ey, ez, tmin;
-};
-
-// Sphere::hit (sphere.rs:39-71) in distance units along the unit direction, with
-// the discriminant from the closest-approach vector (r^2 - |oc - hb e|^2: no
-// cancellation against |oc|^2 for big spheres) and the stable root pair.
-__device__ __forceinline__ void sphere_test(const float4 S, int i, const Seg &g, float &best, int &hid) {
-    const float ocx = g.ox - S.x, ocy = g.oy - S.y, ocz = g.oz - S.z;
-    const float hb = fmaf(ocx, g.ex, fmaf(ocy, g.ey, ocz * g.ez));
-    const float lx = fmaf(-hb, g.ex, ocx), ly = fmaf(-hb, g.ey, ocy), lz = fmaf(-hb, g.ez, ocz);
-    const float rr = S.w * S.w;
-    const float disc = rr - fmaf(lx, lx, fmaf(ly, ly, lz * lz));
-    if (!(disc >= 0.f)) return;
-    const float sq = __builtin_sqrtf(disc);
-    const float c = fmaf(ocx, ocx, fmaf(ocy, ocy, fmaf(ocz, ocz, -rr)));
-    const float q = -hb - copysignf(sq, hb);
-    const float t0 = c * __builtin_amdgcn_rcpf(q), t1 = q;
-    const float tn = fminf(t0, t1), tf = fmaxf(t0, t1);
-    const float t = tn >= g.tmin ? tn : tf;
-    if (t >= g.tmin && t < best) best = t, hid = i;
-}
-
-// Per-segment slab setup for the 4-wide BVH of rtw_accel.h (its boxes are
-// padded for the parity walk; that padding only adds a few box hits here).
-__device__ __forceinline__ void walk_ray(const Seg &g, rtw_accel::WalkRay &r) {
-    using namespace rtw_accel;
-    const float mo = fmax3(fabsf(g.ox), fabsf(g.oy), fabsf(g.oz));
-    r.ox = g.ox, r.oy = g.oy, r.oz = g.oz, r.ex = g.ex, r.ey = g.ey, r.ez = g.ez;
-    r.neg = (g.ex < 0.f ? 1u : 0u) | (g.ey < 0.f ? 2u : 0u) | (g.ez < 0.f ? 4u : 0u);
-    r.ix = rcp32(clamp_dir(g.ex)), r.iy = rcp32(clamp_dir(g.ey)), r.iz = rcp32(clamp_dir(g.ez));
-    const float pad = kPadK * mo + 1e-30f;
-    const float alx = -(g.ox + pad) * r.ix, ahx = -(g.ox - pad) * r.ix;
-    const float aly = -(g.oy + pad) * r.iy, ahy = -(g.oy - pad) * r.iy;
-    const float alz = -(g.oz + pad) * r.iz, ahz = -(g.oz - pad) * r.iz;
-    const bool nx = r.neg & 1u, ny = r.neg & 2u, nz = r.neg & 4u;
-    r.anx = nx ? ahx : alx, r.afx = nx ? alx : ahx;
-    r.any = ny ? ahy : aly, r.afy = ny ? aly : ahy;
-    r.anz = nz ? ahz : alz, r.afz = nz ? alz : ahz;
-    r.tmin = g.tmin * 0.999f;
-    r.negG = 0.f;
-}
-
-// Closest hit: the "always" spheres, then the BVH walk testing leaf spheres as
-// they are reached (the running best is the walk's cut), or a linear scan.
-__device__ __forceinline__ void scene_hit(const FastParams &P, const float4 *__restrict__ geo,
-                                          const float4 *__restrict__ nodes, const Seg &g, float &best,
-                                          int &hid, uint16_t *stk, uint32_t &visits, uint32_t &wvisits) {
-    best = INFINITY, hid = -1;
-    if (P.n_node == 0) {
-        for (uint32_t i = 0; i < P.n_sph; ++i) sphere_test(geo[i], static_cast<int>(i), g, best, hid);
-        return;
-    }
-    for (uint32_t a = 0; a < P.n_always; ++a) {
-        const uint32_t i = P.always[a];
-        sphere_test(geo[i], static_cast<int>(i), g, best, hid);
-    }
-    if (!(rtw_accel::fmax3(fabsf(g.ox), fabsf(g.oy), fabsf(g.oz)) <= rtw_accel::kGuardBvh)) {
-        for (uint32_t i = 0; i < P.n_sph; ++i) sphere_test(geo[i], static_cast<int>(i), g, best, hid);
-        return;
-    }
-    rtw_accel::WalkRay r;
-    walk_ray(g, r);
-    const uint32_t sx = r.neg & 1u, sy = (r.neg >> 1) & 1u, sz = r.neg >> 2;
-    const uint32_t oct_shift = 8u * (r.neg & 3u);
-    const bool oct_hi = r.neg >= 4u;
-    uint16_t *top = stk;
-    uint32_t cur = 0;
-    for (;;) {
-        ++visits;
-#ifdef RTW_FAST_DIAG
-        // wave-level walk iterations, counted by the first active lane (diagnostic
-        // builds: the count costs 2%; 9.4 per wave-iteration against 5.4 visits per lane)
-        if (static_cast<int>(__lane_id()) == __builtin_ctzll(__builtin_amdgcn_read_exec())) ++wvisits;
-#endif
-        uint32_t off;
-        asm("v_mul_u32_u24 %0, 0x90, %1" : "=v"(off) : "v"(cur));
-        const float4 *N = reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(nodes) + off);
-        const float4 nX = N[sx], fX = N[sx ^ 1u], nY = N[2u + sy], fY = N[3u - sy], nZ = N[4u + sz],
-                     fZ = N[5u - sz], qc = N[6], qo = N[7];
-        uint32_t hit = 0;
-        hit |= rtw_accel::slab_hit4(nX, nY, nZ, fX, fY, fZ, r, best);
-        const uint32_t r01w = rtw_accel::as_u32(qc.x), r23w = rtw_accel::as_u32(qc.y);
-        const uint32_t masks = rtw_accel::as_u32(qc.z);
-        hit &= masks;
-        uint32_t lmask = hit & (masks >> 4);
-        const uint32_t inner = hit & ~lmask & 15u;
-        while (lmask) {
-            const uint32_t j = static_cast<uint32_t>(__builtin_ctz(lmask));
-            lmask &= lmask - 1u;
-            const uint32_t k = ((j & 2u ? r23w : r01w) >> (16u * (j & 1u))) & 0xffffu;
-            sphere_test(geo[k], static_cast<int>(k), g, best, hid);
-        }
-        const uint32_t ord = ((oct_hi ? rtw_accel::as_u32(qo.y) : rtw_accel::as_u32(qo.x)) >> oct_shift) & 0xffu;
-        const uint64_t refs = (static_cast<uint64_t>(r23w) << 32) | r01w;
-        for (int t = 3; t >= 0; --t) {  // far to near: the nearest ends on top
-            const uint32_t j = (ord >> (2 * t)) & 3u;
-            *top = static_cast<uint16_t>(refs >> (16u * j));
-            top += __builtin_amdgcn_ubfe(inner, j, 1u) * kBlock;
-        }
-        if (top == stk) break;
-        top -= kBlock;
-        cur = *top;
-    }
-}
 
 template <bool kLds>
 __global__ __launch_bounds__(kBlock, 2) void rtw_fast_render(const FastParams P) {

@@ -915,6 +915,79 @@ std::string render_png_device(const Camera &cam, const Scene &world, uint32_t sa
     }
 }
 
+std::string render_progressive_device(const Camera &cam, const Scene &world, uint32_t samples_sqrt, rtw_u128 seed,
+                                      int device, uint32_t passes, const std::string &preview_dir, bool png,
+                                      std::vector<float> *frame, std::vector<float> *pass_ms, rtw_stats *stats) {
+    DeviceGuard guard;
+    FlatScene flat;
+    world.flatten(flat);
+    rtw_session *s = nullptr;
+    void *d_acc = nullptr, *d_fb = nullptr;
+    auto ok = [](int64_t rc) {
+        if (rc < 0) throw Error(static_cast<int>(rc), last_error());
+        return rc;
+    };
+    try {
+        ok(rtw_session_create(device, &s));
+        ok(rtw_session_set_scene(s, flat.spheres.data(), static_cast<uint32_t>(flat.spheres.size()),
+                                 flat.materials.data(), static_cast<uint32_t>(flat.materials.size())));
+        const uint32_t w = cam.width(), h = cam.height();
+        const uint64_t n = std::max<uint64_t>(static_cast<uint64_t>(w) * h * 3, 1);
+        const uint32_t n_off = samples_sqrt ? samples_sqrt * samples_sqrt : 1;
+        passes = std::min(std::max(passes, 1u), n_off);
+        HIPCHECK(hipSetDevice(device));
+        HIPCHECK(hipMalloc(&d_acc, n * sizeof(unsigned long long)));
+        HIPCHECK(hipMalloc(&d_fb, n * sizeof(float)));
+        HIPCHECK(hipMemset(d_acc, 0, n * sizeof(unsigned long long)));
+        const uint64_t filtered = (1 + 3ull * w) * h;
+        std::string file(filtered + (filtered / kPngTile + 1) * kPngStoredHead + kPngHead + kPngTail, '\0');
+        const size_t cap = file.size();
+        rtw_stats total{};
+        uint64_t done = 0;
+        for (uint32_t p = 0; p < passes; ++p) {  // pass p: the lattice samples k = p (mod passes)
+            const uint32_t k_count = (n_off - p + passes - 1) / passes;
+            ok(rtw_session_accumulate_fast(s, &cam.d, samples_sqrt, seed, nullptr, p, passes, k_count,
+                                           static_cast<unsigned long long *>(d_acc), nullptr));
+            rtw_stats st{};
+            ok(rtw_session_stats(s, &st));  // waits for the pass
+            done += k_count;
+            ok(rtw_resolve_fast(device, static_cast<unsigned long long *>(d_acc), done, w, h,
+                                static_cast<float *>(d_fb), nullptr, nullptr));
+            if (pass_ms) pass_ms->push_back(st.kernel_ms);
+            total.kernel_ms += st.kernel_ms, total.samples += st.samples, total.segments += st.segments;
+            total.pixels = st.pixels;
+            const bool last = p + 1 == passes;
+            if (!preview_dir.empty() || (last && png)) {  // the running mean, as a viewer would see it
+                file.resize(cap);
+                file.resize(static_cast<size_t>(ok(rtw_png_device(device, d_fb, 1, w, h, -1, nullptr, &file[0], cap))));
+            }
+            if (!preview_dir.empty()) {
+                char name[32];
+                std::snprintf(name, sizeof name, "/pass_%04u.png", p);
+                FILE *f = std::fopen((preview_dir + name).c_str(), "wb");
+                if (!f) throw Error(RTW_E_ARG, "cannot create " + preview_dir + name);
+                const bool short_write = std::fwrite(file.data(), 1, file.size(), f) != file.size();
+                if (std::fclose(f) != 0 || short_write) throw Error(RTW_E_ARG, "short write");
+            }
+        }
+        if (stats) *stats = total;
+        if (!png) {
+            HIPCHECK(hipDeviceSynchronize());
+            frame->resize(static_cast<size_t>(w) * h * 3);
+            HIPCHECK(hipMemcpy(frame->data(), d_fb, frame->size() * sizeof(float), hipMemcpyDeviceToHost));
+            file.clear();
+        }
+        (void)hipFree(d_acc), (void)hipFree(d_fb);
+        rtw_session_destroy(s);
+        return file;
+    } catch (...) {
+        if (d_acc) (void)hipFree(d_acc);
+        if (d_fb) (void)hipFree(d_fb);
+        rtw_session_destroy(s);
+        throw;
+    }
+}
+
 }  // namespace rtw
 
 #define RTW_PNG_GUARD(body)             \

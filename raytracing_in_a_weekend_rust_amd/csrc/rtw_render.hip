@@ -3163,9 +3163,10 @@ void render(rtw_session *s, const rtw_camera *cam, uint32_t samples_sqrt, rtw_u1
 }
 
 // f32 fast mode (rtw_fast.hip): same camera, shard and validation as render().
-void render_fast(rtw_session *s, const rtw_camera *cam, uint32_t samples_sqrt, rtw_u128 seed,
-                 const rtw_shard *shard_in, float *out, hipStream_t stream) {
-    if (!cam || !out) throw rtw::Error(RTW_E_ARG, "null argument");
+// Its validation and the launch parameters every fast-mode entry point shares: the
+// camera flattened to f32, the shard, the scene tables and the session's counters.
+rtw_fast::FastParams fast_params(rtw_session *s, const rtw_camera *cam, uint32_t samples_sqrt, rtw_u128 seed,
+                                 const rtw_shard *shard_in) {
     if (!s->scene_set) throw rtw::Error(RTW_E_ARG, "session has no scene");
     if (cam->img_height == 0 || cam->img_width == 0)
         throw rtw::Error(RTW_E_EMPTY_IMAGE, "image height and width must be > 0");  // camera.rs:267
@@ -3211,17 +3212,15 @@ void render_fast(rtw_session *s, const rtw_camera *cam, uint32_t samples_sqrt, r
     F.cmax = static_cast<float>(std::min(65536., 2147483648. / static_cast<double>(F.n_off)));
     F.seed_mix = seed.lo ^ (seed.hi * 0x9e3779b97f4a7c15ull);
     F.geo = s->d_fgeo, F.mat = s->d_fmat, F.kind = s->d_fkind;
-    F.out = out;
     F.cursor = s->d_fcursor;
     F.counters = s->d_fcount;
-    hipStream_t st = stream;
-    HIPCHECK(hipSetDevice(s->device));
-    order_after_last(s, st);
-    HIPCHECK(hipEventRecord(s->ev0, st));
-    HIPCHECK(hipEventRecord(s->ev_k0, st));
-    const rtw::Knobs kn;  // tuning only under RTW_AB (rtw_internal.h)
-    const char *lds_knob = kn.get("RTW_FAST_LDS");
-    HIPCHECK(rtw_fast::launch(F, s->n_cu, st, !(lds_knob && !std::atoi(lds_knob))));
+    return F;
+}
+
+// After a fast-mode launch on st: the latch (every pixel of the shard written or
+// flushed), the closing event and the host half of rtw_stats.
+void finish_fast(rtw_session *s, const rtw_fast::FastParams &F, uint64_t samples_per_pixel, uint32_t lds_bytes,
+                 hipStream_t st) {
     HIPCHECK(hipEventRecord(s->ev_k1, st));
     hipLaunchKernelGGL(rtw_latch_check<unsigned long long>, dim3(1), dim3(64), 0, st,
                        static_cast<const unsigned long long *>(s->d_fcount + 2),
@@ -3232,15 +3231,59 @@ void render_fast(rtw_session *s, const rtw_camera *cam, uint32_t samples_sqrt, r
     s->pending = true;
     s->last = rtw_stats{};
     s->last.pixels = static_cast<uint64_t>(F.n_rows) * F.W;
-    s->last.samples = s->last.pixels * F.n_off;
+    s->last.samples = s->last.pixels * samples_per_pixel;
     s->last.grid_blocks = static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>(s->n_cu > 0 ? s->n_cu : 256) * 2,
                                                                    (s->last.pixels + 7) / 8));
     s->last.block_threads = rtw_fast::kBlock;
     s->last.accel = F.n_node ? 2u : 0u;
-    bool in_lds = false;
-    s->last.lds_bytes = static_cast<uint32_t>(rtw_fast::lds_bytes(F.n_sph, F.n_node, F.n_stack, &in_lds));
+    s->last.lds_bytes = lds_bytes;
     s->last_fast = true;
     s->main_ev = true;
+}
+
+void render_fast(rtw_session *s, const rtw_camera *cam, uint32_t samples_sqrt, rtw_u128 seed,
+                 const rtw_shard *shard_in, float *out, hipStream_t stream) {
+    if (!cam || !out) throw rtw::Error(RTW_E_ARG, "null argument");
+    rtw_fast::FastParams F = fast_params(s, cam, samples_sqrt, seed, shard_in);
+    F.out = out;
+    hipStream_t st = stream;
+    HIPCHECK(hipSetDevice(s->device));
+    order_after_last(s, st);
+    HIPCHECK(hipEventRecord(s->ev0, st));
+    HIPCHECK(hipEventRecord(s->ev_k0, st));
+    const rtw::Knobs kn;  // tuning only under RTW_AB (rtw_internal.h)
+    const char *lds_knob = kn.get("RTW_FAST_LDS");
+    HIPCHECK(rtw_fast::launch(F, s->n_cu, st, !(lds_knob && !std::atoi(lds_knob))));
+    bool in_lds = false;
+    finish_fast(s, F, F.n_off, static_cast<uint32_t>(rtw_fast::lds_bytes(F.n_sph, F.n_node, F.n_stack, &in_lds)), st);
+}
+
+// Progressive fast mode (rtw_fast_acc.hip): lattice samples k_first + i k_step, i < k_count,
+// of every pixel of the shard added to the caller's fixed-point sums.
+void accumulate_fast(rtw_session *s, const rtw_camera *cam, uint32_t samples_sqrt, rtw_u128 seed,
+                     const rtw_shard *shard_in, uint32_t k_first, uint32_t k_step, uint32_t k_count,
+                     unsigned long long *acc, hipStream_t st) {
+    if (!cam || !acc) throw rtw::Error(RTW_E_ARG, "null argument");
+    if (k_step == 0 && k_count > 1) throw rtw::Error(RTW_E_ARG, "k_step is 0 with k_count > 1");
+    rtw_fast::AccParams A{};
+    A.f = fast_params(s, cam, samples_sqrt, seed, shard_in);
+    if (k_count && static_cast<uint64_t>(k_first) + static_cast<uint64_t>(k_count - 1) * k_step >= A.f.n_off)
+        throw rtw::Error(RTW_E_ARG, "lattice samples beyond samples_sqrt^2");
+    // the pixel cursor is 32 bits and every wave steps past the end once
+    if (static_cast<uint64_t>(cam->img_height) * cam->img_width >= (1ull << 32) - (1u << 24))
+        throw rtw::Error(RTW_E_UNSUPPORTED, "progressive fast mode: image too large");
+    A.k_first = k_first, A.k_step = k_step, A.k_count = k_count;
+    A.acc = acc;
+    HIPCHECK(hipSetDevice(s->device));
+    order_after_last(s, st);
+    HIPCHECK(hipEventRecord(s->ev0, st));
+    HIPCHECK(hipEventRecord(s->ev_k0, st));
+    const rtw::Knobs kn;  // tuning only under RTW_AB (rtw_internal.h)
+    const char *lds_knob = kn.get("RTW_FAST_LDS");
+    HIPCHECK(rtw_fast::launch_accumulate(A, s->n_cu, st, !(lds_knob && !std::atoi(lds_knob))));
+    if (k_count == 0) A.f.n_rows = 0;  // nothing launched, nothing flushed: the latch expects 0 pixels
+    bool in_lds = false;
+    finish_fast(s, A.f, k_count, static_cast<uint32_t>(rtw_fast::acc_lds_bytes(A.f.n_sph, A.f.n_node, A.f.n_stack, &in_lds)), st);
 }
 
 // Latched incomplete renders since the last check (rtw_latch_check): reported
@@ -3533,6 +3576,32 @@ int rtw_session_render_fast(rtw_session *s, const rtw_camera *cam, uint32_t samp
     if (!s) return rtw::set_error("null session"), RTW_E_ARG;
     RTW_GUARD_BEGIN
     render_fast(s, cam, samples_sqrt, seed, shard, out_rgb_device, static_cast<hipStream_t>(hip_stream));
+    return RTW_OK;
+    RTW_GUARD_END
+}
+
+int rtw_session_accumulate_fast(rtw_session *s, const rtw_camera *cam, uint32_t samples_sqrt, rtw_u128 seed,
+                                const rtw_shard *shard, uint32_t k_first, uint32_t k_step, uint32_t k_count,
+                                unsigned long long *acc_device, void *hip_stream) {
+    if (!s) return rtw::set_error("null session"), RTW_E_ARG;
+    RTW_GUARD_BEGIN
+    accumulate_fast(s, cam, samples_sqrt, seed, shard, k_first, k_step, k_count, acc_device,
+                    static_cast<hipStream_t>(hip_stream));
+    return RTW_OK;
+    RTW_GUARD_END
+}
+
+int rtw_resolve_fast(int device, const unsigned long long *acc_device, uint64_t n_samples, uint32_t width,
+                     uint32_t height, float *out_rgb_device, uint8_t *preview_rgba8_device, void *hip_stream) {
+    RTW_GUARD_BEGIN
+    if (!acc_device || (!out_rgb_device && !preview_rgba8_device)) throw rtw::Error(RTW_E_ARG, "null argument");
+    if (n_samples == 0) throw rtw::Error(RTW_E_ARG, "n_samples is 0");
+    if (width == 0 || height == 0) throw rtw::Error(RTW_E_EMPTY_IMAGE, "image height and width must be > 0");
+    if (reinterpret_cast<uintptr_t>(preview_rgba8_device) % 4) throw rtw::Error(RTW_E_ARG, "preview buffer not 4-byte aligned");
+    HIPCHECK(hipSetDevice(device));
+    HIPCHECK(rtw_fast::launch_resolve(acc_device, n_samples, static_cast<uint64_t>(width) * height, out_rgb_device,
+                                      reinterpret_cast<uint32_t *>(preview_rgba8_device),
+                                      static_cast<hipStream_t>(hip_stream)));
     return RTW_OK;
     RTW_GUARD_END
 }
