@@ -446,6 +446,96 @@ int rtw_resolve_fast(int device, const unsigned long long *acc_device, uint64_t 
                      uint32_t width, uint32_t height, float *out_rgb_device,
                      uint8_t *preview_rgba8_device, void *hip_stream);
 
+/* ---- adaptive fast mode (ABI 7 additions) ----
+ * Samples go only to the pixels whose mean is still noisy. Let N = max(1, samples_sqrt^2);
+ * the adaptive calls need N <= 65535 (a larger N is RTW_E_UNSUPPORTED). Three caller-owned
+ * device buffers extend acc (rows*W*3 u64); pixel indices are shard-local and row-major:
+ *   counts  rows*W u32: the samples each pixel has so far.
+ *   mom     rows*W*2 u64. A finished sample with fixed-point channels R, G, B (what is added
+ *           to acc) has q = min((R+G+B) >> 16, 2^24 - 1), its luminance sum in units of
+ *           2^-16; mom[p][0] += q, mom[p][1] += q*q. With n <= 65535 samples neither sum
+ *           overflows: q^2 < 2^48.
+ * Sample order. A pixel's i-th sample (i = 0, 1, ...) is lattice sample k = (i*k_mul) mod N
+ *   (the product in 64 bits), gcd(k_mul, N) = 1: every k once, and the first few spread over
+ *   the lattice instead of coming from its first rows.
+ * Convergence. Exact unsigned 128-bit integer arithmetic (mod 2^128). With n = counts[p],
+ *   A = mom[p][0], B = mom[p][1], T = tol_q16 <= 65535 (the relative standard error of the
+ *   mean, units of 2^-16) and F = floor_q16 <= 2^24 (a luminance floor in q units, so dark
+ *   pixels do not sample forever):
+ *     D = n*B - A*A,  E = (A + n*F) >> 8,
+ *     conv(p) <=> T > 0 and n >= 2 and (D << 16) <= T*T*(n-1)*E*E,
+ *   which is sigma_mean <= t*(mu + f) with both sides scaled by n^2 (n-1) 2^16. Bit budget
+ *   for sums the accumulate built: A < 2^40, B < 2^64, 0 <= D < 2^80 so D*2^16 < 2^96;
+ *   E < 2^33, so the right side < 2^32 * 2^16 * 2^66 = 2^114. T = 0: never converged.
+ * Selection. u(p) = n < N and not conv(p); listed(p) = n < N and u holds for p or for any of
+ *   its up-to-8 neighbours inside the rows*W buffer (the usual guard against a pixel that
+ *   stops early by luck). A list holds the listed pixels in ascending order. */
+
+/* The default k_mul: 1 for N <= 2, else the integer coprime to N nearest to
+ * N*(sqrt(5)-1)/2 (evaluated in IEEE double), ties to the lower. Host only, needs no GPU. */
+uint32_t rtw_lattice_stride(uint32_t N);
+
+/* For every pixel p of the list, with n0 = counts[p]: traces ordinals [n0, min(n0+m, N)),
+ * adds their colours to acc and q, q*q to mom, and stores the new count. A pixel outside
+ * the list is not touched. list_device: n_list u32 on the device, each pixel at most once;
+ * n_list_device: the length, a u32 on the device (the host need not know it). A NULL
+ * list_device means every pixel of the shard (n_list_device is then ignored). Every m in
+ * 1..65535 is served by one kernel built for m >= 16; below that it keeps 8*m lanes of a
+ * wave busy. Asynchronous on hip_stream. Ordering, latch and rtw_session_stats as for
+ * rtw_session_accumulate_fast; samples is the number actually traced.
+ * Errors, found before any device work: rtw_session_accumulate_fast's checks; a null acc,
+ * mom or counts, m == 0 or m > 65535, or gcd(k_mul, N) != 1 is RTW_E_ARG. */
+int rtw_session_accumulate_fast_list(rtw_session *s, const rtw_camera *cam, uint32_t samples_sqrt,
+                                     rtw_u128 seed, const rtw_shard *shard,
+                                     const uint32_t *list_device, const uint32_t *n_list_device,
+                                     uint32_t m, uint32_t k_mul, unsigned long long *acc_device,
+                                     unsigned long long *mom_device, uint32_t *counts_device,
+                                     void *hip_stream);
+
+/* Writes the listed pixels (ascending) to list_out_device (room for rows*width u32) and their
+ * number to n_list_out_device (one u32). Asynchronous on hip_stream: two passes over one bit
+ * per pixel, a scan and an emit. Scratch lives in a per-device context the library owns
+ * (rtw_shutdown frees it); calls on one device are serialised and ordered on the device
+ * across streams, and the caller's current HIP device is restored.
+ * Errors: a null pointer, a mom_device that is not 16-byte aligned (a pixel's two sums are
+ * read as one), N == 0, tol_q16 > 65535 or floor_q16 > 2^24 is RTW_E_ARG;
+ * N > 65535 RTW_E_UNSUPPORTED; width or rows 0 RTW_E_EMPTY_IMAGE. */
+int rtw_adaptive_select(int device, const uint32_t *counts_device,
+                        const unsigned long long *mom_device, uint32_t width, uint32_t rows,
+                        uint32_t N, uint32_t tol_q16, uint32_t floor_q16,
+                        uint32_t *list_out_device, uint32_t *n_list_out_device, void *hip_stream);
+
+/* rtw_resolve_fast with the divisor read per pixel from counts_device: the same expression,
+ * (float)((double)acc * 2^-32 / (double)n), and the same RGBA8 rule. A pixel with count 0
+ * resolves to 0. Errors as rtw_resolve_fast. */
+int rtw_resolve_fast_counts(int device, const unsigned long long *acc_device,
+                            const uint32_t *counts_device, uint32_t width, uint32_t rows,
+                            float *out_rgb_device, uint8_t *preview_rgba8_device,
+                            void *hip_stream);
+
+typedef struct rtw_adaptive_info {
+    uint32_t rounds;      /* accumulate launches, the first (every pixel) included        */
+    uint32_t selects;     /* selections run                                               */
+    uint64_t samples;     /* samples traced = the sum of the final counts                 */
+    uint64_t pixels_full; /* pixels that reached N                                        */
+    double kernel_ms;     /* the accumulate kernels, summed, from HIP events              */
+    double select_ms;     /* the selections, summed, from HIP events                      */
+} rtw_adaptive_info;
+
+/* The driver; it blocks. On buffers the session owns: zero acc, mom and counts; one round over
+ * every pixel with m = min(max(min_samples, 2), N); then select, read the 4-byte list length
+ * and, while it is not 0, accumulate the list with m = batch; at the end resolve by counts
+ * into out_rgb_device (rows*W*3 f32) and copy the counts to counts_out_device (rows*W u32,
+ * nullable). k_mul = rtw_lattice_stride(N). With tol_q16 = 0 every pixel reaches N and the
+ * frame is rtw_session_render_fast's bit for bit. info is nullable.
+ * Errors: rtw_session_accumulate_fast_list's and rtw_adaptive_select's; batch == 0 or
+ * batch > 65535 is RTW_E_ARG. */
+int rtw_session_render_fast_adaptive(rtw_session *s, const rtw_camera *cam, uint32_t samples_sqrt,
+                                     rtw_u128 seed, const rtw_shard *shard, uint32_t tol_q16,
+                                     uint32_t floor_q16, uint32_t min_samples, uint32_t batch,
+                                     float *out_rgb_device, uint32_t *counts_out_device,
+                                     void *hip_stream, rtw_adaptive_info *info);
+
 /* ---- device probes (tests) ---- */
 /* Device jump-ahead seeds (the kernel's own code path) for a pixel range. */
 int rtw_probe_device_seeds(int device, rtw_u128 seed, uint64_t first_pixel, uint64_t count,

@@ -107,6 +107,14 @@ class PngStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class AdaptiveInfo(C.Structure):
+    _fields_ = [("rounds", C.c_uint32), ("selects", C.c_uint32), ("samples", C.c_uint64),
+                ("pixels_full", C.c_uint64), ("kernel_ms", C.c_double), ("select_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 GATHER_NAMES = {0: "none", 1: "copy", 2: "rccl"}
 FALLBACK_NAMES = {0: "none", 1: "rccl_unloadable", 2: "comm_init_failed"}
 GROUP_COPY_GATHER = 1
@@ -178,6 +186,17 @@ SIGNATURES = {
                                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rtw_resolve_fast": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),
+    "rtw_lattice_stride": (C.c_uint32, [C.c_uint32]),
+    "rtw_session_accumulate_fast_list": (C.c_int, [C.c_void_p, _P(Camera), C.c_uint32, U128, _P(Shard), C.c_void_p,
+                                                   C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p]),
+    "rtw_adaptive_select": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                      C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtw_resolve_fast_counts": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+    "rtw_session_render_fast_adaptive": (C.c_int, [C.c_void_p, _P(Camera), C.c_uint32, U128, _P(Shard), C.c_uint32,
+                                                   C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, _P(AdaptiveInfo)]),
     "rtw_session_stats": (C.c_int, [C.c_void_p, _P(Stats)]),
     "rtw_session_diag": (C.c_int, [C.c_void_p, _P(C.c_uint32), C.c_uint64]),
     "rtw_quantise_device": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p,

@@ -13,6 +13,7 @@ with the matching RTW_E_* code.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -383,6 +384,35 @@ def resolve_fast(acc_ptr: int, shape, n_samples: int, out_ptr: int = 0, preview_
                                C.c_void_p(preview_ptr or None), C.c_void_p(stream or 0)))
 
 
+def lattice_stride(n: int) -> int:
+    """rtw_lattice_stride: the default sample-order multiplier of an n-sample lattice (no GPU needed)."""
+    return lib.rtw_lattice_stride(n)
+
+
+def to_q16(v: float, limit: int) -> int:
+    """The one conversion of a tolerance or luminance floor given as a fraction to the C ABI's
+    q16 argument: round(v * 65536), clamped to [0, limit]."""
+    return min(limit, max(0, int(math.floor(v * 65536. + 0.5))))
+
+
+def adaptive_select(counts_ptr: int, mom_ptr: int, shape, n: int, tol_q16: int, floor_q16: int, list_ptr: int,
+                    n_list_ptr: int, device: int = 0, stream: int = 0):
+    """rtw_adaptive_select: the pixels of the (rows, w) buffers that still need samples, ascending,
+    to list_ptr (rows*w u32) and their number to n_list_ptr (one u32), asynchronously on `stream`."""
+    h, w = shape
+    check(lib.rtw_adaptive_select(device, C.c_void_p(counts_ptr), C.c_void_p(mom_ptr), w, h, n, tol_q16, floor_q16,
+                                  C.c_void_p(list_ptr), C.c_void_p(n_list_ptr), C.c_void_p(stream or 0)))
+
+
+def resolve_fast_counts(acc_ptr: int, counts_ptr: int, shape, out_ptr: int = 0, preview_ptr: int = 0, device: int = 0,
+                        stream: int = 0):
+    """rtw_resolve_fast_counts: resolve_fast with each pixel divided by its own count (0 resolves to 0)."""
+    h, w = shape
+    check(lib.rtw_resolve_fast_counts(device, C.c_void_p(acc_ptr), C.c_void_p(counts_ptr), w, h,
+                                      C.c_void_p(out_ptr or None), C.c_void_p(preview_ptr or None),
+                                      C.c_void_p(stream or 0)))
+
+
 class Session:
     """Device-resident rendering (rtw_session_*): the scene lives in HBM; renders
     are enqueued on a caller HIP stream into a caller device buffer."""
@@ -420,6 +450,39 @@ class Session:
         check(lib.rtw_session_accumulate_fast(self.h, C.byref(cam), samples_sqrt, capi.U128.of(seed),
                                               C.byref(sh) if sh is not None else None, k_first, k_step,
                                               k_count, C.c_void_p(acc_ptr), C.c_void_p(stream or 0)))
+
+    def accumulate_fast_list(self, cam: capi.Camera, samples_sqrt: int, seed: int, acc_ptr: int, mom_ptr: int,
+                             counts_ptr: int, m: int, k_mul: int | None = None, list_ptr: int = 0, n_list_ptr: int = 0,
+                             shard=None, stream: int = 0):
+        """Adds the next m samples (ordinal i is lattice sample i*k_mul mod N; default k_mul:
+        lattice_stride(N)) of the pixels in the device list (list_ptr 0: every pixel) to the sums,
+        the luminance moments (n_rows x W x 2 u64) and the counts (n_rows x W u32)."""
+        if k_mul is None:
+            k_mul = lattice_stride(max(1, samples_sqrt * samples_sqrt))
+        sh = _shard(shard)
+        check(lib.rtw_session_accumulate_fast_list(self.h, C.byref(cam), samples_sqrt, capi.U128.of(seed),
+                                                   C.byref(sh) if sh is not None else None,
+                                                   C.c_void_p(list_ptr or None), C.c_void_p(n_list_ptr or None), m, k_mul,
+                                                   C.c_void_p(acc_ptr or None), C.c_void_p(mom_ptr or None),
+                                                   C.c_void_p(counts_ptr or None), C.c_void_p(stream or 0)))
+
+    def render_fast_adaptive(self, cam: capi.Camera, samples_sqrt: int, seed: int, tol: float, floor: float = 0.05,
+                             min_samples: int = 16, batch: int = 16):
+        """rtw_session_render_fast_adaptive (blocking): every pixel sampled until the relative
+        standard error of its mean luminance sum is <= tol (against mean + floor), or the
+        lattice is used up. tol and floor are fractions (to_q16). Returns (frame f32 (h, w, 3),
+        counts int32 (h, w), info dict), torch tensors on the current device."""
+        import torch
+        h, w = cam.img_height, cam.img_width
+        frame = torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
+        counts = torch.empty((h, w), dtype=torch.int32, device="cuda")
+        info = capi.AdaptiveInfo()
+        check(lib.rtw_session_render_fast_adaptive(self.h, C.byref(cam), samples_sqrt, capi.U128.of(seed), None,
+                                                   to_q16(tol, 65535), to_q16(floor, 1 << 24), min_samples, batch,
+                                                   C.c_void_p(frame.data_ptr()), C.c_void_p(counts.data_ptr()),
+                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream or 0),
+                                                   C.byref(info)))
+        return frame, counts, info.as_dict()
 
     def progressive_fast(self, cam: capi.Camera, samples_sqrt: int, seed: int, passes: int):
         """Renders the lattice in `passes` strided passes (pass p: k = p mod passes) and

@@ -14,7 +14,10 @@
 // precedence over the PPM), --passes N (fast mode, one device: the lattice in N strided
 // passes whose sums add up to the same file, each pass's kernel time printed) and
 // --preview-dir DIR (with it: the running mean after every pass as DIR/pass_%04u.png, the
-// headless stand-in for the reference's preview window). --preview is accepted and
+// headless stand-in for the reference's preview window), --adaptive TOL (fast mode, one
+// device: every pixel sampled until the relative standard error of its mean is <= TOL or the
+// lattice is used up, rtw_session_render_fast_adaptive; --min-samples M and --batch B set the
+// first round's and the later rounds' samples per pixel). --preview is accepted and
 // ignored: the winit window itself (application/mod.rs) is out of scope.
 #include <chrono>
 #include <cstdio>
@@ -38,6 +41,9 @@ struct Config {  // main.rs:13-29
     bool png = false, out_set = false;
     uint32_t passes = 0;  // > 0: progressive fast mode
     std::string preview_dir;
+    bool adaptive = false;
+    double tol = 0.;
+    uint32_t min_samples = 16, batch = 16;
     std::vector<int> devices;  // empty: every visible device (--device-ppm: device 0)
 };
 
@@ -134,6 +140,17 @@ Config parse_args(int argc, char **argv) {
         else if (a == "--png") c.png = true;
         else if (a == "--passes") need(c.passes, "--passes");
         else if (a == "--preview-dir" && next) c.preview_dir = next;
+        else if (a == "--adaptive") {
+            char *end = nullptr;
+            c.tol = next ? std::strtod(next, &end) : -1.;
+            if (!next || end == next || *end || !(c.tol >= 0.)) {
+                std::fprintf(stderr, "Usage: --adaptive <tolerance, e.g. 0.05>\n");
+                std::exit(1);
+            }
+            c.adaptive = true;
+        }
+        else if (a == "--min-samples") need(c.min_samples, "--min-samples");
+        else if (a == "--batch") need(c.batch, "--batch");
         else if (a == "--help") {
             std::printf("Use the application like this:\n");
             std::printf("\t-h --height\t:\tSet the height of the image\n");
@@ -150,12 +167,19 @@ Config parse_args(int argc, char **argv) {
             std::printf("\t--png\t\t:\tone GPU; the frame is encoded to a PNG file there; takes precedence over the PPM\n");
             std::printf("\t--passes N\t:\tfast mode, one GPU: render in N passes over the whole lattice (same file)\n");
             std::printf("\t--preview-dir D\t:\twith --passes: the image so far after each pass as D/pass_NNNN.png\n");
+            std::printf("\t--adaptive TOL\t:\tfast mode, one GPU: sample each pixel to a relative standard error of TOL\n");
+            std::printf("\t--min-samples M\t:\twith --adaptive: samples every pixel gets first (default 16)\n");
+            std::printf("\t--batch B\t:\twith --adaptive: samples per listed pixel and round (default 16)\n");
             std::exit(0);
         }
     }
     if (!c.preview_dir.empty() && !c.passes) c.passes = 1;
     if (c.passes && (!c.fast || c.device_ppm || c.devices.size() > 1)) {
         std::fprintf(stderr, "--passes and --preview-dir need --mode fast on one device, without --device-ppm\n");
+        std::exit(1);
+    }
+    if (c.adaptive && (!c.fast || c.passes || c.devices.size() > 1)) {
+        std::fprintf(stderr, "--adaptive needs --mode fast on one device, without --passes\n");
         std::exit(1);
     }
     if ((c.device_ppm || c.png) && c.devices.size() > 1) {  // the frame of a multi-device render is gathered on the host
@@ -195,7 +219,26 @@ int main(int argc, char **argv) {
             b.cam.width(), b.cam.height(), cfg.sample_sqrt * cfg.sample_sqrt, b.cam.d.max_depth);
         rtw_stats st{};
         const auto t0 = std::chrono::steady_clock::now();
-        if (cfg.passes) {
+        if (cfg.adaptive) {
+            std::vector<float> f32;
+            rtw_adaptive_info info{};
+            const std::string file = rtw::render_adaptive_device(
+                b.cam, *b.world, cfg.sample_sqrt, seed, cfg.devices.empty() ? 0 : cfg.devices[0], cfg.tol, 0.05,
+                cfg.min_samples, cfg.batch, cfg.png ? 2 : (cfg.device_ppm ? 1 : 0), &f32, &info, &st);
+            std::printf("adaptive: %u rounds, %llu samples, %.2f mean samples per pixel\n", info.rounds,
+                        static_cast<unsigned long long>(info.samples),
+                        static_cast<double>(info.samples) / static_cast<double>(st.pixels ? st.pixels : 1));
+            if (cfg.png || cfg.device_ppm) {
+                FILE *f = std::fopen(cfg.out.c_str(), "wb");
+                if (!f) throw rtw::Error(RTW_E_ARG, "cannot create " + cfg.out);
+                const bool short_write = std::fwrite(file.data(), 1, file.size(), f) != file.size();
+                if (std::fclose(f) != 0 || short_write) throw rtw::Error(RTW_E_ARG, "short write");
+            } else {
+                const std::vector<double> fb(f32.begin(), f32.end());
+                const int rc = rtw_write_ppm(cfg.out.c_str(), fb.data(), b.cam.width(), b.cam.height());
+                if (rc != RTW_OK) throw rtw::Error(rc, rtw_last_error());
+            }
+        } else if (cfg.passes) {
             std::vector<float> f32, ms;
             const std::string png = rtw::render_progressive_device(b.cam, *b.world, cfg.sample_sqrt, seed,
                                                                    cfg.devices.empty() ? 0 : cfg.devices[0], cfg.passes,

@@ -44,6 +44,7 @@
 #include "rtw_accel.h"
 #include "rtw_capi.h"
 #include "rtw_fast.h"
+#include "rtw_fast_adapt.h"
 #include "rtw_numeric.h"
 #include "rtw_ppm.h"
 #include "host/rtw_host.h"
@@ -2515,6 +2516,14 @@ struct rtw_session {
     uint32_t *d_fkind = nullptr, *d_fcursor = nullptr;
     unsigned long long *d_fcount = nullptr;
     bool last_fast = false;
+    bool last_list = false;  // the last fast launch was a list accumulate: samples come from its counter
+    // adaptive fast mode's driver (rtw_fast_adapt.h): sums, moments, counts, list (grow-only),
+    // the list's length + the count of finished pixels, and the length's pinned host copy
+    unsigned long long *d_aacc = nullptr, *d_amom = nullptr, *d_afull = nullptr;
+    uint32_t *d_acounts = nullptr, *d_alist = nullptr, *d_an = nullptr;
+    unsigned long long *h_an = nullptr;
+    size_t adapt_cap = 0;
+    hipEvent_t ev_s0 = nullptr, ev_s1 = nullptr;  // around a selection
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr;  // around the main kernel (rtw_stats.main_kernel_ms)
     // the seed kernel runs on `aux` beside the cost probe (fork / join events on the
@@ -3238,6 +3247,7 @@ void finish_fast(rtw_session *s, const rtw_fast::FastParams &F, uint64_t samples
     s->last.accel = F.n_node ? 2u : 0u;
     s->last.lds_bytes = lds_bytes;
     s->last_fast = true;
+    s->last_list = false;
     s->main_ev = true;
 }
 
@@ -3286,6 +3296,113 @@ void accumulate_fast(rtw_session *s, const rtw_camera *cam, uint32_t samples_sqr
     finish_fast(s, A.f, k_count, static_cast<uint32_t>(rtw_fast::acc_lds_bytes(A.f.n_sph, A.f.n_node, A.f.n_stack, &in_lds)), st);
 }
 
+// Adaptive fast mode (rtw_fast_adapt.hip): the next m samples, in the order i -> (i k_mul) mod N,
+// of the pixels of a device list (null: every pixel), with moments and counts beside the sums.
+void accumulate_fast_list(rtw_session *s, const rtw_camera *cam, uint32_t samples_sqrt, rtw_u128 seed,
+                          const rtw_shard *shard_in, const uint32_t *list, const uint32_t *n_list, uint32_t m,
+                          uint32_t k_mul, unsigned long long *acc, unsigned long long *mom, uint32_t *counts,
+                          hipStream_t st) {
+    if (!cam || !acc || !mom || !counts) throw rtw::Error(RTW_E_ARG, "null argument");
+    if (list && !n_list) throw rtw::Error(RTW_E_ARG, "a list without its length");
+    if (m == 0 || m > 65535) throw rtw::Error(RTW_E_ARG, "m outside 1..65535");
+    rtw_fast::ListParams A{};
+    A.f = fast_params(s, cam, samples_sqrt, seed, shard_in);
+    if (A.f.n_off > 65535) throw rtw::Error(RTW_E_UNSUPPORTED, "adaptive fast mode: more than 65535 samples per pixel");
+    uint32_t a = k_mul, b = A.f.n_off;
+    while (b) {
+        const uint32_t t = a % b;
+        a = b, b = t;
+    }
+    if (a != 1) throw rtw::Error(RTW_E_ARG, "k_mul is not coprime to samples_sqrt^2");
+    // the entry cursor is 32 bits and every wave steps past the end once
+    if (static_cast<uint64_t>(cam->img_height) * cam->img_width >= (1ull << 32) - (1u << 24))
+        throw rtw::Error(RTW_E_UNSUPPORTED, "adaptive fast mode: image too large");
+    A.list = list, A.n_list = n_list;
+    A.m = m, A.k_mul = k_mul % A.f.n_off;  // the same order; the kernel's products stay below 2^32
+    A.acc = acc, A.mom = mom, A.counts = counts;
+    HIPCHECK(hipSetDevice(s->device));
+    order_after_last(s, st);
+    HIPCHECK(hipEventRecord(s->ev0, st));
+    HIPCHECK(hipEventRecord(s->ev_k0, st));
+    const rtw::Knobs kn;  // tuning only under RTW_AB (rtw_internal.h)
+    const char *lds_knob = kn.get("RTW_FAST_LDS");
+    HIPCHECK(rtw_fast::launch_accumulate_list(A, s->n_cu, st, !(lds_knob && !std::atoi(lds_knob))));
+    bool in_lds = false;
+    finish_fast(s, A.f, 0, static_cast<uint32_t>(rtw_fast::list_lds_bytes(A.f.n_sph, A.f.n_node, A.f.n_stack, &in_lds)), st);
+    s->last_list = true;
+}
+
+void check_latch(rtw_session *s);
+void collect(rtw_session *s);
+
+// The adaptive driver: rounds of accumulate_fast_list and rtw_adaptive_select on buffers the
+// session owns, until no pixel is listed; it waits for each round's list length.
+void render_fast_adaptive(rtw_session *s, const rtw_camera *cam, uint32_t samples_sqrt, rtw_u128 seed,
+                          const rtw_shard *shard_in, uint32_t tol_q16, uint32_t floor_q16, uint32_t min_samples,
+                          uint32_t batch, float *out, uint32_t *counts_out, hipStream_t st, rtw_adaptive_info *info) {
+    if (!cam || !out) throw rtw::Error(RTW_E_ARG, "null argument");
+    if (batch == 0 || batch > 65535) throw rtw::Error(RTW_E_ARG, "batch outside 1..65535");
+    if (tol_q16 > 65535u || floor_q16 > (1u << 24)) throw rtw::Error(RTW_E_ARG, "tol_q16 > 65535 or floor_q16 > 2^24");
+    const rtw_fast::FastParams F = fast_params(s, cam, samples_sqrt, seed, shard_in);  // the checks, and the shard
+    const uint32_t N = F.n_off;
+    if (N > 65535) throw rtw::Error(RTW_E_UNSUPPORTED, "adaptive fast mode: more than 65535 samples per pixel");
+    const size_t npix = static_cast<size_t>(F.n_rows) * F.W;
+    rtw_adaptive_info I{};
+    HIPCHECK(hipSetDevice(s->device));
+    if (!s->h_an) {
+        HIPCHECK(hipHostMalloc(&s->h_an, 2 * sizeof(unsigned long long)));
+        HIPCHECK(hipMalloc(&s->d_an, sizeof(uint32_t)));
+        HIPCHECK(hipMalloc(&s->d_afull, sizeof(unsigned long long)));
+        HIPCHECK(hipEventCreate(&s->ev_s0));
+        HIPCHECK(hipEventCreate(&s->ev_s1));
+    }
+    if (npix > s->adapt_cap) {
+        dev_free(s->d_aacc), dev_free(s->d_amom), dev_free(s->d_acounts), dev_free(s->d_alist);
+        s->d_aacc = s->d_amom = nullptr, s->d_acounts = s->d_alist = nullptr, s->adapt_cap = 0;
+        HIPCHECK(hipMalloc(&s->d_aacc, npix * 3 * sizeof(unsigned long long)));
+        HIPCHECK(hipMalloc(&s->d_amom, npix * 2 * sizeof(unsigned long long)));
+        HIPCHECK(hipMalloc(&s->d_acounts, npix * sizeof(uint32_t)));
+        HIPCHECK(hipMalloc(&s->d_alist, npix * sizeof(uint32_t)));
+        s->adapt_cap = npix;
+    }
+    if (npix) {
+        order_after_last(s, st);
+        HIPCHECK(hipMemsetAsync(s->d_aacc, 0, npix * 3 * sizeof(unsigned long long), st));
+        HIPCHECK(hipMemsetAsync(s->d_amom, 0, npix * 2 * sizeof(unsigned long long), st));
+        HIPCHECK(hipMemsetAsync(s->d_acounts, 0, npix * sizeof(uint32_t), st));
+        HIPCHECK(hipMemsetAsync(s->d_afull, 0, sizeof(unsigned long long), st));
+        const uint32_t k_mul = rtw_lattice_stride(N);
+        auto round = [&](const uint32_t *list, uint32_t m) {
+            accumulate_fast_list(s, cam, samples_sqrt, seed, shard_in, list, s->d_an, m, k_mul, s->d_aacc, s->d_amom,
+                                 s->d_acounts, st);
+            collect(s);  // waits; the round's samples and kernel time
+            ++I.rounds, I.samples += s->last.samples, I.kernel_ms += s->last.main_kernel_ms;
+        };
+        round(nullptr, std::min(std::max(min_samples, 2u), N));
+        for (;;) {
+            HIPCHECK(hipEventRecord(s->ev_s0, st));
+            const int rc = rtw_adaptive_select(s->device, s->d_acounts, s->d_amom, F.W, F.n_rows, N, tol_q16, floor_q16,
+                                               s->d_alist, s->d_an, st);
+            if (rc != RTW_OK) throw rtw::Error(rc, rtw::last_error());
+            HIPCHECK(hipEventRecord(s->ev_s1, st));
+            HIPCHECK(hipMemcpyAsync(s->h_an, s->d_an, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIPCHECK(hipStreamSynchronize(st));
+            float ms = 0.f;
+            HIPCHECK(hipEventElapsedTime(&ms, s->ev_s0, s->ev_s1));
+            ++I.selects, I.select_ms += ms;
+            if (*reinterpret_cast<const uint32_t *>(s->h_an) == 0) break;
+            round(s->d_alist, batch);
+        }
+        HIPCHECK(rtw_fast::launch_resolve_counts(s->d_aacc, s->d_acounts, npix, out, nullptr, N, s->d_afull, st));
+        if (counts_out)
+            HIPCHECK(hipMemcpyAsync(counts_out, s->d_acounts, npix * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        HIPCHECK(hipMemcpyAsync(s->h_an + 1, s->d_afull, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipStreamSynchronize(st));
+        I.pixels_full = s->h_an[1];
+    }
+    if (info) *info = I;
+}
+
 // Latched incomplete renders since the last check (rtw_latch_check): reported
 // once, then cleared.
 void check_latch(rtw_session *s) {
@@ -3307,7 +3424,7 @@ void collect(rtw_session *s) {
     float main_ms = 0.f;
     if (s->main_ev) HIPCHECK(hipEventElapsedTime(&main_ms, s->ev_k0, s->ev_k1));
     if (s->last_fast) {
-        unsigned long long c[5] = {};
+        unsigned long long c[6] = {};
         HIPCHECK(hipMemcpy(c, s->d_fcount, sizeof c, hipMemcpyDeviceToHost));
         float ms = 0.f;
         HIPCHECK(hipEventElapsedTime(&ms, s->ev0, s->ev1));
@@ -3318,6 +3435,7 @@ void collect(rtw_session *s) {
         s->last.sphere_tests = c[0] * s->n_sph;
         s->last.kernel_ms = ms;
         s->last.main_kernel_ms = main_ms;
+        if (s->last_list) s->last.samples = c[5];  // what the list kernel traced
         if (c[2] != s->last.pixels)  // never a silently incomplete image
             throw rtw::Error(RTW_E_HIP, "fast render incomplete: " + std::to_string(c[2]) + " of " +
                                             std::to_string(s->last.pixels) + " pixels written");
@@ -3539,6 +3657,11 @@ int rtw_session_destroy(rtw_session *s) {
     dev_free(s->d_park_flag), dev_free(s->d_order), dev_free(s->d_cost), dev_free(s->d_cost_hist);
     dev_free(s->d_pcost), dev_free(s->d_err);
     dev_free(s->d_fcursor), dev_free(s->d_fcount);
+    dev_free(s->d_aacc), dev_free(s->d_amom), dev_free(s->d_afull), dev_free(s->d_acounts), dev_free(s->d_alist);
+    dev_free(s->d_an);
+    if (s->h_an) (void)hipHostFree(s->h_an);
+    if (s->ev_s0) (void)hipEventDestroy(s->ev_s0);
+    if (s->ev_s1) (void)hipEventDestroy(s->ev_s1);
     if (s->ev0) (void)hipEventDestroy(s->ev0);
     if (s->ev1) (void)hipEventDestroy(s->ev1);
     if (s->ev_k0) (void)hipEventDestroy(s->ev_k0);
@@ -3606,6 +3729,30 @@ int rtw_resolve_fast(int device, const unsigned long long *acc_device, uint64_t 
     RTW_GUARD_END
 }
 
+int rtw_session_accumulate_fast_list(rtw_session *s, const rtw_camera *cam, uint32_t samples_sqrt, rtw_u128 seed,
+                                     const rtw_shard *shard, const uint32_t *list_device, const uint32_t *n_list_device,
+                                     uint32_t m, uint32_t k_mul, unsigned long long *acc_device,
+                                     unsigned long long *mom_device, uint32_t *counts_device, void *hip_stream) {
+    if (!s) return rtw::set_error("null session"), RTW_E_ARG;
+    RTW_GUARD_BEGIN
+    accumulate_fast_list(s, cam, samples_sqrt, seed, shard, list_device, n_list_device, m, k_mul, acc_device,
+                         mom_device, counts_device, static_cast<hipStream_t>(hip_stream));
+    return RTW_OK;
+    RTW_GUARD_END
+}
+
+int rtw_session_render_fast_adaptive(rtw_session *s, const rtw_camera *cam, uint32_t samples_sqrt, rtw_u128 seed,
+                                     const rtw_shard *shard, uint32_t tol_q16, uint32_t floor_q16, uint32_t min_samples,
+                                     uint32_t batch, float *out_rgb_device, uint32_t *counts_out_device, void *hip_stream,
+                                     rtw_adaptive_info *info) {
+    if (!s) return rtw::set_error("null session"), RTW_E_ARG;
+    RTW_GUARD_BEGIN
+    render_fast_adaptive(s, cam, samples_sqrt, seed, shard, tol_q16, floor_q16, min_samples, batch, out_rgb_device,
+                         counts_out_device, static_cast<hipStream_t>(hip_stream), info);
+    return RTW_OK;
+    RTW_GUARD_END
+}
+
 int rtw_session_stats(rtw_session *s, rtw_stats *out) {
     if (!s || !out) return rtw::set_error("null argument"), RTW_E_ARG;
     RTW_GUARD_BEGIN
@@ -3663,6 +3810,7 @@ int rtw_shutdown(void) {
     for (auto *s : g_multi) rtw_session_destroy(s);
     g_multi.clear();
     rtw::ppm_shutdown();  // the device output stage's per-device contexts (rtw_ppm.hip)
+    rtw::adapt_shutdown();  // the adaptive selection's (rtw_fast_adapt.hip)
     return RTW_OK;
 }
 
