@@ -1,8 +1,9 @@
 // rtw_internal.h -- shared between the host mirror (rtw_host.cpp) and the device
-// half of the C ABI (rtw_render.hip, rtw_group.hip). Not part of the public ABI.
+// half of the C ABI (the .hip files). Not part of the public ABI.
 #pragma once
 
 #include <algorithm>
+#include <cstdint>
 #include <cstdlib>
 #include <stdexcept>
 #include <string>
@@ -49,4 +50,39 @@ struct Knobs {
     }
     const char *get(const char *name) const { return on ? std::getenv(name) : nullptr; }
 };
+
+inline uint32_t gcd_u32(uint32_t a, uint32_t b) {
+    while (b) {
+        const uint32_t t = a % b;
+        a = b, b = t;
+    }
+    return a;
+}
 }  // namespace rtw
+
+// ---- the .hip files' host halves
+#define HIPCHECK(expr)                                                                      \
+    do {                                                                                    \
+        hipError_t e_ = (expr);                                                             \
+        if (e_ != hipSuccess)                                                               \
+            throw rtw::Error(RTW_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+
+namespace rtw {
+// The caller's current device is restored on every exit (the calls switch devices; a
+// torch caller's allocations must not move).
+struct DeviceGuard {
+    int dev = -1;
+    DeviceGuard() {
+        if (hipGetDevice(&dev) != hipSuccess) dev = -1;
+    }
+    ~DeviceGuard() {
+        if (dev >= 0) (void)hipSetDevice(dev);
+    }
+};
+}  // namespace rtw
+using rtw::DeviceGuard;
+#endif

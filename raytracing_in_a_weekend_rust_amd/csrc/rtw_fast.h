@@ -45,9 +45,10 @@ constexpr uint32_t kLdsCap = 79 * 1024;  // two workgroups per CU (160 KB), with
 static_assert(kBlock % 8 == 0, "stack area alignment");
 constexpr uint32_t stack_slots(uint32_t depth) { return 3 * depth + 2; }
 
-// Dynamic LDS bytes of a launch: the stacks, plus the scene tables when they fit
-// (*scene_in_lds); otherwise the kernel reads the scene from global memory.
-size_t lds_bytes(uint32_t n_sph, uint32_t n_node, uint32_t n_stack, bool *scene_in_lds);
+// Dynamic LDS bytes of a launch: the stacks, plus the scene tables when both fit below
+// the kernel's cap (*scene_in_lds; kLdsCap, kAccLdsCap, kListLdsCap); otherwise the kernel
+// reads the scene from global memory.
+size_t lds_bytes(uint32_t n_sph, uint32_t n_node, uint32_t n_stack, uint32_t cap, bool *scene_in_lds);
 
 // Enqueues the render (zeroes the cursor and counters first).
 hipError_t launch(const FastParams &P, int n_cu, hipStream_t st, bool scene_lds = true);
@@ -69,8 +70,6 @@ constexpr uint32_t kAccLaneMax = 16;
 constexpr uint32_t kAccRing = 8;
 // two workgroups per CU with the ring sums (8 waves x kAccRing x 3 u64) beside them
 constexpr uint32_t kAccLdsCap = 80 * 1024 - (kBlock / 64) * kAccRing * 3 * 8;
-
-size_t acc_lds_bytes(uint32_t n_sph, uint32_t n_node, uint32_t n_stack, bool *scene_in_lds);
 
 // Enqueues the accumulation (zeroes the cursor and counters first); k_count = 0 launches nothing.
 hipError_t launch_accumulate(const AccParams &A, int n_cu, hipStream_t st, bool scene_lds = true);

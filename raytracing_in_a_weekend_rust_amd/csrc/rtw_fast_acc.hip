@@ -32,46 +32,6 @@
 namespace rtw_fast {
 namespace {
 
-// Scene tables and the BVH into LDS behind the per-lane stacks (as rtw_fast_render).
-template <bool kLds>
-__device__ __forceinline__ void stage_scene(const FastParams &P, float4 *lds, uint32_t tid, const float4 *&geo,
-                                            const float4 *&mat, const float4 *&nodes, const uint32_t *&kind) {
-    geo = P.geo, mat = P.mat, nodes = P.nodes, kind = P.kind;
-    if constexpr (kLds) {
-        float4 *g = lds + P.n_stack * kBlock * sizeof(uint16_t) / sizeof(float4);
-        float4 *m = g + P.n_sph, *nd = m + P.n_sph;
-        uint32_t *kd = reinterpret_cast<uint32_t *>(nd + P.n_node * rtw_accel::kNodeF4);
-        for (uint32_t i = tid; i < P.n_sph; i += kBlock) g[i] = P.geo[i], m[i] = P.mat[i], kd[i] = P.kind[i];
-        for (uint32_t i = tid; i < P.n_node * rtw_accel::kNodeF4; i += kBlock) nd[i] = P.nodes[i];
-        geo = g, mat = m, nodes = nd, kind = kd;
-        __syncthreads();
-    }
-}
-
-__device__ __forceinline__ uint32_t rank_in(uint64_t mask) {  // set bits of mask below this lane
-    return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32),
-                                     __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0u));
-}
-
-// statistics: one atomic per wave and counter (FastParams::counters)
-__device__ __forceinline__ void add_counters(const FastParams &P, uint32_t lane, uint32_t segs, uint32_t visits,
-                                             uint32_t written, uint32_t iters, uint32_t wvisits, bool lane_written) {
-    unsigned long long sg = segs, vs = visits, wv = wvisits, wr = written;
-    for (int o = 32; o > 0; o >>= 1) {
-        sg += __shfl_xor(sg, o);
-        vs += __shfl_xor(vs, o);
-        wv += __shfl_xor(wv, o);
-        if (lane_written) wr += __shfl_xor(wr, o);  // else wave-uniform already
-    }
-    if (lane == 0) {
-        atomicAdd(P.counters + 0, sg);
-        atomicAdd(P.counters + 1, vs);
-        atomicAdd(P.counters + 2, wr);
-        atomicAdd(P.counters + 3, static_cast<unsigned long long>(iters));
-        atomicAdd(P.counters + 4, wv);
-    }
-}
-
 // ---- a lane owns a pixel (k_count < kAccLaneMax)
 template <bool kLds>
 __global__ __launch_bounds__(kBlock, 2) void rtw_fast_acc_lane(const AccParams A) {
@@ -130,138 +90,46 @@ __global__ __launch_bounds__(kBlock, 2) void rtw_fast_acc_lane(const AccParams A
             }
         }
     }
-    add_counters(P, lane, segs, visits, written, iters, wvisits, true);
+    add_counters(P, lane, WaveStats{segs, visits, iters, wvisits}, written, true);
 }
 
-// ---- a wave shares a ring of pixels (k_count >= kAccLaneMax)
+// ---- a wave shares a ring of pixels (k_count >= kAccLaneMax): rtw_fast_dev.h's scheduler;
+// chunked pixels, the pass's samples, and the three sums added to the buffer by three lanes
+struct Pass : RgbSums {
+    struct Job {
+        uint32_t pix;
+    };
+    static constexpr uint32_t kRing = kAccRing;
+    const AccParams &A;
+    const uint32_t npix;
+    ChunkCursor cursor;
+    __device__ __forceinline__ Claim claim(uint32_t lane, Job &j) {
+        return cursor.next(A.f, lane, A.chunk, npix, j.pix) ? Claim::kJob : Claim::kDone;
+    }
+    __device__ __forceinline__ uint32_t count(const Job &) const { return A.k_count; }
+    __device__ __forceinline__ uint32_t lattice(const Job &, uint32_t i) const { return A.k_first + i * A.k_step; }
+    __device__ __forceinline__ void flush(uint32_t lane, const Job &j, const unsigned long long *a) const {
+        if (lane < 3) A.acc[static_cast<uint64_t>(j.pix) * 3u + lane] += a[lane];
+    }
+};
+
 template <bool kLds>
 __global__ __launch_bounds__(kBlock, 2) void rtw_fast_acc_ring(const AccParams A) {
-    extern __shared__ __attribute__((aligned(16))) float4 lds[];
-    __shared__ unsigned long long acc[kWaves][kAccRing][3];
-    const FastParams &P = A.f;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    uint16_t *stk = reinterpret_cast<uint16_t *>(lds) + tid;
-    const float4 *geo, *mat, *nodes;
-    const uint32_t *kind;
-    stage_scene<kLds>(P, lds, tid, geo, mat, nodes, kind);
-    const uint32_t npix = P.n_rows * P.W;
-    const float cmax = P.cmax;
-    // wave-uniform ring state: pixel and samples in flight per slot, the slot being
-    // handed out (cs), its pixel and the next sample index of it
-    uint32_t pixs[kAccRing], outst[kAccRing];
-#pragma unroll
-    for (uint32_t s = 0; s < kAccRing; ++s) pixs[s] = kFree, outst[s] = 0;
-    uint32_t cs = kFree, cur_pix = 0, next = 0;
-    uint32_t claim = 0, claim_end = 0;  // the wave's pixels claimed from the cursor and not yet started
-    bool exhausted = false;
-    Seg g{};
-    float tr = 0.f, tg = 0.f, tb = 0.f;
-    uint32_t depth = 0, slot = kFree;
-    Rng rng{1u, 0u};
-    uint32_t segs = 0, visits = 0, written = 0, iters = 0, wvisits = 0;
-    for (;;) {
-        // ---- hand out samples of the newest pixel to idle lanes
-        for (;;) {
-            const uint64_t need = __ballot(slot == kFree);
-            if (need == 0) break;
-            if (cs == kFree || next >= A.k_count) {
-                if (exhausted) break;
-                uint32_t f = kFree;
-#pragma unroll
-                for (uint32_t s = 0; s < kAccRing; ++s)
-                    if (f == kFree && pixs[s] == kFree) f = s;
-                if (f == kFree) break;
-                if (claim == claim_end) {  // A.chunk pixels per atomic: every wave draws from one address
-                    uint32_t c = 0;
-                    if (lane == 0) c = atomicAdd(P.cursor, A.chunk);
-                    c = __builtin_amdgcn_readfirstlane(c);
-                    if (c >= npix) {
-                        exhausted = true;
-                        break;
-                    }
-                    claim = c, claim_end = min(c + A.chunk, npix);
-                }
-                const uint32_t p = claim++;
-#pragma unroll
-                for (uint32_t s = 0; s < kAccRing; ++s)
-                    if (s == f) pixs[s] = p, outst[s] = 0;
-                if (lane < 3) acc[wave][f][lane] = 0ull;
-                __builtin_amdgcn_wave_barrier();
-                cs = f, cur_pix = p, next = 0;
-            }
-            const uint32_t rank = rank_in(need);
-            const uint32_t avail = A.k_count - next;
-            if (slot == kFree && rank < avail) {
-                start_path(P, cur_pix, A.k_first + (next + rank) * A.k_step, rng, g);
-                tr = tg = tb = 1.f;
-                depth = 0;
-                slot = cs;
-            }
-            const uint32_t took = min(static_cast<uint32_t>(__builtin_popcountll(need)), avail);
-            next += took;
-#pragma unroll
-            for (uint32_t s = 0; s < kAccRing; ++s)
-                if (s == cs) outst[s] += took;
-        }
-        if (__ballot(slot != kFree) == 0) break;  // nothing handed out: the shard is done
-        ++iters;
-        // ---- one segment per busy lane; finished samples into their pixel's sum
-        float cr = 0.f, cg = 0.f, cb = 0.f;
-        const bool fin = slot != kFree && trace_segment(P, geo, mat, kind, nodes, g, rng, tr, tg, tb, depth, stk, segs,
-                                                        visits, wvisits, cr, cg, cb);
-        if (fin) {
-            unsigned long long *a = acc[wave][slot];
-            atomicAdd(a + 0, to_fixed(cr, cmax));
-            atomicAdd(a + 1, to_fixed(cg, cmax));
-            atomicAdd(a + 2, to_fixed(cb, cmax));
-        }
-#pragma unroll
-        for (uint32_t s = 0; s < kAccRing; ++s)
-            outst[s] -= static_cast<uint32_t>(__builtin_popcountll(__ballot(fin && slot == s)));
-        if (fin) slot = kFree;
-        // ---- pixels whose samples are all handed out and finished: add to the buffer
-#pragma unroll
-        for (uint32_t s = 0; s < kAccRing; ++s) {
-            if (pixs[s] != kFree && outst[s] == 0 && (s != cs || next >= A.k_count)) {
-                __builtin_amdgcn_wave_barrier();
-                if (lane < 3) A.acc[static_cast<uint64_t>(pixs[s]) * 3u + lane] += acc[wave][s][lane];
-                pixs[s] = kFree;
-                ++written;
-                if (s == cs) cs = kFree;
-            }
-        }
-    }
-    add_counters(P, lane, segs, visits, written, iters, wvisits, false);
+    Pass u{{}, A, A.f.n_rows * A.f.W, {}};
+    uint32_t written;
+    const WaveStats w = run_ring<kLds>(A.f, u, written);
+    add_counters(A.f, threadIdx.x & 63u, w, written, false);
 }
 
 // ---- sums to images: one thread per pixel
-__device__ __forceinline__ uint32_t preview_u8(float mean) {  // Rust's `(mean as f64 * 255.) as u8`
-    const double v = static_cast<double>(mean) * 255.;
-    return v >= 255. ? 255u : (v > 0. ? static_cast<uint32_t>(v) : 0u);  // NaN -> 0
-}
-
 __global__ __launch_bounds__(256) void rtw_fast_resolve(const unsigned long long *__restrict__ acc, double n,
                                                         uint64_t n_pixels, float *__restrict__ out,
                                                         uint32_t *__restrict__ preview) {
     const uint64_t p = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
-    if (p >= n_pixels) return;
-    float m[3];
-#pragma unroll
-    for (uint32_t c = 0; c < 3; ++c)  // the one-shot kernel's expression (rtw_fast.hip), an IEEE f64 divide
-        m[c] = static_cast<float>(static_cast<double>(acc[p * 3u + c]) * (1. / 4294967296.) / n);
-    if (out) out[p * 3u + 0] = m[0], out[p * 3u + 1] = m[1], out[p * 3u + 2] = m[2];
-    if (preview) preview[p] = preview_u8(m[0]) | (preview_u8(m[1]) << 8) | (preview_u8(m[2]) << 16) | 0xff000000u;
+    if (p < n_pixels) resolve_pixel(acc, p, n, out, preview);
 }
 
 }  // namespace
-
-size_t acc_lds_bytes(uint32_t n_sph, uint32_t n_node, uint32_t n_stack, bool *scene_in_lds) {
-    const size_t stacks = static_cast<size_t>(n_stack) * kBlock * sizeof(uint16_t);
-    const size_t scene = static_cast<size_t>(n_sph) * (2 * sizeof(float4) + sizeof(uint32_t)) +
-                         static_cast<size_t>(n_node) * rtw_accel::kNodeF4 * sizeof(float4);
-    *scene_in_lds = stacks + scene <= kAccLdsCap;
-    return *scene_in_lds ? stacks + scene : (stacks ? stacks : 16);
-}
 
 hipError_t launch_accumulate(const AccParams &A_in, int n_cu, hipStream_t st, bool scene_lds) {
     AccParams A = A_in;
@@ -269,30 +137,13 @@ hipError_t launch_accumulate(const AccParams &A_in, int n_cu, hipStream_t st, bo
     // ring pixels a wave claims per cursor atomic: about 256 samples' worth, 1 from 256 samples
     // per pixel on (the one-shot kernel's hand-out), never more than 16
     A.chunk = std::min(16u, std::max(1u, 256u / std::max(A.k_count, 1u)));
-    hipError_t e = hipMemsetAsync(P.cursor, 0, sizeof(uint32_t), st);
-    if (e == hipSuccess) e = hipMemsetAsync(P.counters, 0, 5 * sizeof(unsigned long long), st);
-    if (e != hipSuccess) return e;
-    if (P.n_rows == 0 || P.W == 0 || A.k_count == 0) return hipSuccess;
-    const bool by_lane = A.k_count < kAccLaneMax;
-    const uint64_t npix = static_cast<uint64_t>(P.n_rows) * P.W;
+    const bool nothing = P.n_rows == 0 || P.W == 0 || A.k_count == 0;
     // a wave starts on 64 pixels (lane) or 1 (ring): no more workgroups than have work
-    const uint64_t per_block = by_lane ? kBlock : kWaves;
-    const uint32_t blocks = static_cast<uint32_t>(
-        std::min<uint64_t>(static_cast<uint64_t>(n_cu > 0 ? n_cu : 256) * 2, (npix + per_block - 1) / per_block));
-    bool in_lds = false;
-    size_t lds = acc_lds_bytes(P.n_sph, P.n_node, P.n_stack, &in_lds);
-    if (!scene_lds && in_lds) {
-        in_lds = false;
-        lds = P.n_stack ? static_cast<size_t>(P.n_stack) * kBlock * sizeof(uint16_t) : 16;
-    }
-    if (by_lane) {
-        if (in_lds) hipLaunchKernelGGL(rtw_fast_acc_lane<true>, dim3(blocks), dim3(kBlock), lds, st, A);
-        else hipLaunchKernelGGL(rtw_fast_acc_lane<false>, dim3(blocks), dim3(kBlock), lds, st, A);
-    } else {
-        if (in_lds) hipLaunchKernelGGL(rtw_fast_acc_ring<true>, dim3(blocks), dim3(kBlock), lds, st, A);
-        else hipLaunchKernelGGL(rtw_fast_acc_ring<false>, dim3(blocks), dim3(kBlock), lds, st, A);
-    }
-    return hipGetLastError();
+    if (A.k_count < kAccLaneMax)
+        return launch_persistent(rtw_fast_acc_lane<true>, rtw_fast_acc_lane<false>, A, P, nothing, 5, kBlock, kAccLdsCap,
+                                 n_cu, st, scene_lds);
+    return launch_persistent(rtw_fast_acc_ring<true>, rtw_fast_acc_ring<false>, A, P, nothing, 5, kWaves, kAccLdsCap,
+                             n_cu, st, scene_lds);
 }
 
 hipError_t launch_resolve(const unsigned long long *acc, uint64_t n_samples, uint64_t n_pixels, float *out_rgb,

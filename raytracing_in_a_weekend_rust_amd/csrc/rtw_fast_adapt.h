@@ -26,8 +26,6 @@ constexpr uint32_t kListSums = 5;  // R, G, B, q, q^2
 // two workgroups per CU with the ring sums (8 waves x kListRing x kListSums u64) beside them
 constexpr uint32_t kListLdsCap = 80 * 1024 - (kBlock / 64) * kListRing * kListSums * 8;
 
-size_t list_lds_bytes(uint32_t n_sph, uint32_t n_node, uint32_t n_stack, bool *scene_in_lds);
-
 // Enqueues the accumulation. Zeroes the cursor and f.counters[0..5] first; [2] ends as
 // n_rows * W when every list entry was served (the latch's test), [5] as the samples traced.
 hipError_t launch_accumulate_list(const ListParams &A, int n_cu, hipStream_t st, bool scene_lds = true);

@@ -43,34 +43,53 @@ namespace {
 
 typedef unsigned __int128 u128;
 
-// Scene tables and the BVH into LDS behind the per-lane stacks (as rtw_fast_render).
-template <bool kLds>
-__device__ __forceinline__ void stage_scene(const FastParams &P, float4 *lds, uint32_t tid, const float4 *&geo,
-                                            const float4 *&mat, const float4 *&nodes, const uint32_t *&kind) {
-    geo = P.geo, mat = P.mat, nodes = P.nodes, kind = P.kind;
-    if constexpr (kLds) {
-        float4 *g = lds + P.n_stack * kBlock * sizeof(uint16_t) / sizeof(float4);
-        float4 *m = g + P.n_sph, *nd = m + P.n_sph;
-        uint32_t *kd = reinterpret_cast<uint32_t *>(nd + P.n_node * rtw_accel::kNodeF4);
-        for (uint32_t i = tid; i < P.n_sph; i += kBlock) g[i] = P.geo[i], m[i] = P.mat[i], kd[i] = P.kind[i];
-        for (uint32_t i = tid; i < P.n_node * rtw_accel::kNodeF4; i += kBlock) nd[i] = P.nodes[i];
-        geo = g, mat = m, nodes = nd, kind = kd;
-        __syncthreads();
+// ---- samples for the pixels of a list: what rtw_fast_dev.h's ring scheduler claims, adds
+// and flushes here
+struct List {
+    struct Job {
+        uint32_t pix, first, end;  // the pixel's ordinals [first, end); end is its count after the round
+    };
+    static constexpr uint32_t kRing = kListRing, kSums = kListSums;
+    const ListParams &A;
+    const uint32_t npix, n_ent, chunk;
+    ChunkCursor cursor;
+    uint32_t served = 0, traced = 0;
+    __device__ __forceinline__ Claim claim(uint32_t lane, Job &j) {
+        uint32_t e;
+        if (!cursor.next(A.f, lane, chunk, n_ent, e)) return Claim::kDone;
+        const uint32_t p = A.list ? __builtin_amdgcn_readfirstlane(A.list[e]) : e;
+        ++served;
+        // an entry that is no pixel of the shard, or a pixel at the lattice's end, gets nothing
+        const uint32_t n0 = p < npix ? __builtin_amdgcn_readfirstlane(A.counts[p]) : A.f.n_off;
+        if (n0 >= A.f.n_off) return Claim::kSkip;
+        j = Job{p, n0, n0 + min(A.m, A.f.n_off - n0)};
+        traced += j.end - j.first;
+        return Claim::kJob;
     }
-}
+    __device__ __forceinline__ uint32_t count(const Job &j) const { return j.end - j.first; }
+    // ordinal i is lattice sample (i k_mul) mod n_off; i, k_mul < 2^16: the product fits 32 bits
+    __device__ __forceinline__ uint32_t lattice(const Job &j, uint32_t i) const {
+        return ((j.first + i) * A.k_mul) % A.f.n_off;
+    }
+    static __device__ __forceinline__ void add(unsigned long long *a, unsigned long long r, unsigned long long g,
+                                               unsigned long long b) {
+        const unsigned long long q = min((r + g + b) >> 16, (1ull << 24) - 1ull);
+        RgbSums::add(a, r, g, b);
+        atomicAdd(a + 3, q);
+        atomicAdd(a + 4, q * q);
+    }
+    // six lanes: five plain read-add-writes and the count's store
+    __device__ __forceinline__ void flush(uint32_t lane, const Job &j, const unsigned long long *a) const {
+        const uint64_t p = j.pix;
+        if (lane < 3) A.acc[p * 3u + lane] += a[lane];
+        else if (lane < kListSums) A.mom[p * 2u + (lane - 3u)] += a[lane];
+        else if (lane == kListSums) A.counts[p] = j.end;
+    }
+};
 
-__device__ __forceinline__ uint32_t rank_in(uint64_t mask) {  // set bits of mask below this lane
-    return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32),
-                                     __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0u));
-}
-
-// ---- samples for the pixels of a list
 template <bool kLds>
 __global__ __launch_bounds__(kBlock, 2) void rtw_fast_acc_list(const ListParams A) {
-    extern __shared__ __attribute__((aligned(16))) float4 lds[];
-    __shared__ unsigned long long sums[kWaves][kListRing][kListSums];
     const FastParams &P = A.f;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t npix = P.n_rows * P.W;
     // a list of distinct pixels is no longer than the shard; a null list is every pixel
     const uint32_t n_ent = A.list ? min(__builtin_amdgcn_readfirstlane(*A.n_list), npix) : npix;
@@ -79,131 +98,14 @@ __global__ __launch_bounds__(kBlock, 2) void rtw_fast_acc_list(const ListParams 
     const uint32_t chunk = min(A.chunk, max(1u, n_ent / (gridDim.x * kWaves)));
     // every workgroup before this one has a chunk per wave to claim: nothing is left here
     if (blockIdx.x != 0 && static_cast<uint64_t>(blockIdx.x) * kWaves * chunk >= n_ent) return;
-    uint16_t *stk = reinterpret_cast<uint16_t *>(lds) + tid;
-    const float4 *geo, *mat, *nodes;
-    const uint32_t *kind;
-    stage_scene<kLds>(P, lds, tid, geo, mat, nodes, kind);
-    const float cmax = P.cmax;
-    const uint32_t n_off = P.n_off;
-    // wave-uniform ring state: per slot its pixel, the count it will have after this round
-    // and the samples in flight; the slot being handed out (cs), its pixel, first ordinal,
-    // number of samples and the next of them
-    uint32_t pixs[kListRing], newc[kListRing], outst[kListRing];
-#pragma unroll
-    for (uint32_t s = 0; s < kListRing; ++s) pixs[s] = kFree, newc[s] = 0, outst[s] = 0;
-    uint32_t cs = kFree, cur_pix = 0, cur_first = 0, cur_cnt = 0, next = 0;
-    uint32_t claim = 0, claim_end = 0;  // the wave's entries claimed from the cursor and not yet started
-    bool exhausted = false;
-    Seg g{};
-    float tr = 0.f, tg = 0.f, tb = 0.f;
-    uint32_t depth = 0, slot = kFree;
-    Rng rng{1u, 0u};
-    uint32_t segs = 0, visits = 0, served = 0, iters = 0, wvisits = 0, traced = 0;
-    for (;;) {
-        // ---- hand out samples of the newest pixel to idle lanes
-        for (;;) {
-            const uint64_t need = __ballot(slot == kFree);
-            if (need == 0) break;
-            if (cs == kFree || next >= cur_cnt) {
-                if (exhausted) break;
-                uint32_t f = kFree;
-#pragma unroll
-                for (uint32_t s = 0; s < kListRing; ++s)
-                    if (f == kFree && pixs[s] == kFree) f = s;
-                if (f == kFree) break;
-                if (claim == claim_end) {  // chunk entries per atomic: every wave draws from one address
-                    uint32_t c = 0;
-                    if (lane == 0) c = atomicAdd(P.cursor, chunk);
-                    c = __builtin_amdgcn_readfirstlane(c);
-                    if (c >= n_ent) {
-                        exhausted = true;
-                        break;
-                    }
-                    claim = c, claim_end = min(c + chunk, n_ent);
-                }
-                const uint32_t e = claim++;
-                const uint32_t p = A.list ? __builtin_amdgcn_readfirstlane(A.list[e]) : e;
-                ++served;
-                // an entry that is no pixel of the shard, or a pixel at the lattice's end, gets nothing
-                const uint32_t n0 = p < npix ? __builtin_amdgcn_readfirstlane(A.counts[p]) : n_off;
-                if (n0 >= n_off) continue;
-                const uint32_t cnt = min(A.m, n_off - n0);
-#pragma unroll
-                for (uint32_t s = 0; s < kListRing; ++s)
-                    if (s == f) pixs[s] = p, newc[s] = n0 + cnt, outst[s] = 0;
-                if (lane < kListSums) sums[wave][f][lane] = 0ull;
-                __builtin_amdgcn_wave_barrier();
-                cs = f, cur_pix = p, cur_first = n0, cur_cnt = cnt, next = 0;
-                traced += cnt;
-            }
-            const uint32_t rank = rank_in(need);
-            const uint32_t avail = cur_cnt - next;
-            if (slot == kFree && rank < avail) {
-                // ordinal i is lattice sample (i k_mul) mod n_off; i, k_mul < 2^16: the product fits 32 bits
-                const uint32_t k = ((cur_first + next + rank) * A.k_mul) % n_off;
-                start_path(P, cur_pix, k, rng, g);
-                tr = tg = tb = 1.f;
-                depth = 0;
-                slot = cs;
-            }
-            const uint32_t took = min(static_cast<uint32_t>(__builtin_popcountll(need)), avail);
-            next += took;
-#pragma unroll
-            for (uint32_t s = 0; s < kListRing; ++s)
-                if (s == cs) outst[s] += took;
-        }
-        if (__ballot(slot != kFree) == 0) break;  // nothing handed out: the list is done
-        ++iters;
-        // ---- one segment per busy lane; finished samples into their pixel's sums
-        float cr = 0.f, cg = 0.f, cb = 0.f;
-        const bool fin = slot != kFree && trace_segment(P, geo, mat, kind, nodes, g, rng, tr, tg, tb, depth, stk, segs,
-                                                        visits, wvisits, cr, cg, cb);
-        if (fin) {
-            const unsigned long long r = to_fixed(cr, cmax), gr = to_fixed(cg, cmax), b = to_fixed(cb, cmax);
-            const unsigned long long q = min((r + gr + b) >> 16, (1ull << 24) - 1ull);
-            unsigned long long *a = sums[wave][slot];
-            atomicAdd(a + 0, r);
-            atomicAdd(a + 1, gr);
-            atomicAdd(a + 2, b);
-            atomicAdd(a + 3, q);
-            atomicAdd(a + 4, q * q);
-        }
-#pragma unroll
-        for (uint32_t s = 0; s < kListRing; ++s)
-            outst[s] -= static_cast<uint32_t>(__builtin_popcountll(__ballot(fin && slot == s)));
-        if (fin) slot = kFree;
-        // ---- pixels whose samples are all handed out and finished: sums, moments and count
-#pragma unroll
-        for (uint32_t s = 0; s < kListRing; ++s) {
-            if (pixs[s] != kFree && outst[s] == 0 && (s != cs || next >= cur_cnt)) {
-                __builtin_amdgcn_wave_barrier();
-                const uint64_t p = pixs[s];
-                if (lane < 3) A.acc[p * 3u + lane] += sums[wave][s][lane];
-                else if (lane < kListSums) A.mom[p * 2u + (lane - 3u)] += sums[wave][s][lane];
-                else if (lane == kListSums) A.counts[p] = newc[s];
-                pixs[s] = kFree;
-                if (s == cs) cs = kFree;
-            }
-        }
-    }
-    // statistics: one atomic per wave and counter. [2] counts every pixel that needs nothing
-    // more from this launch: the served entries, and once the pixels outside the list.
-    unsigned long long sg = segs, vs = visits, wv = wvisits;
-    for (int o = 32; o > 0; o >>= 1) {
-        sg += __shfl_xor(sg, o);
-        vs += __shfl_xor(vs, o);
-        wv += __shfl_xor(wv, o);
-    }
-    if (lane == 0) {
-        unsigned long long done = served;
-        if (blockIdx.x == 0 && wave == 0) done += npix - n_ent;
-        atomicAdd(P.counters + 0, sg);
-        atomicAdd(P.counters + 1, vs);
-        atomicAdd(P.counters + 2, done);
-        atomicAdd(P.counters + 3, static_cast<unsigned long long>(iters));
-        atomicAdd(P.counters + 4, wv);
-        atomicAdd(P.counters + 5, static_cast<unsigned long long>(traced));
-    }
+    List u{A, npix, n_ent, chunk, {}};
+    uint32_t flushed;
+    const WaveStats w = run_ring<kLds>(P, u, flushed);
+    // [2] counts every pixel that needs nothing more from this launch: the served entries, and
+    // once the pixels outside the list
+    unsigned long long done = u.served;
+    if (blockIdx.x == 0 && threadIdx.x < 64u) done += npix - n_ent;
+    add_counters(P, threadIdx.x & 63u, w, done, false, u.traced);
 }
 
 // ---- selection
@@ -303,11 +205,6 @@ __global__ __launch_bounds__(kSelBlock) void rtw_adapt_emit(const unsigned long 
 }
 
 // ---- sums to images with a per-pixel divisor: one thread per pixel
-__device__ __forceinline__ uint32_t preview_u8(float mean) {  // Rust's `(mean as f64 * 255.) as u8`
-    const double v = static_cast<double>(mean) * 255.;
-    return v >= 255. ? 255u : (v > 0. ? static_cast<uint32_t>(v) : 0u);  // NaN -> 0
-}
-
 __global__ __launch_bounds__(256) void rtw_fast_resolve_counts(const unsigned long long *__restrict__ acc,
                                                                const uint32_t *__restrict__ counts, uint64_t n_pixels,
                                                                float *__restrict__ out, uint32_t *__restrict__ preview,
@@ -318,47 +215,18 @@ __global__ __launch_bounds__(256) void rtw_fast_resolve_counts(const unsigned lo
         const uint64_t at_end = __ballot(p < n_pixels && n >= n_off);
         if ((threadIdx.x & 63u) == 0 && at_end) atomicAdd(full, static_cast<unsigned long long>(__builtin_popcountll(at_end)));
     }
-    if (p >= n_pixels) return;
-    float m[3];
-#pragma unroll
-    for (uint32_t c = 0; c < 3; ++c)  // rtw_fast_resolve's expression, an IEEE f64 divide
-        m[c] = n ? static_cast<float>(static_cast<double>(acc[p * 3u + c]) * (1. / 4294967296.) / static_cast<double>(n))
-                 : 0.f;
-    if (out) out[p * 3u + 0] = m[0], out[p * 3u + 1] = m[1], out[p * 3u + 2] = m[2];
-    if (preview) preview[p] = preview_u8(m[0]) | (preview_u8(m[1]) << 8) | (preview_u8(m[2]) << 16) | 0xff000000u;
+    if (p < n_pixels) resolve_pixel(acc, p, static_cast<double>(n), out, preview);
 }
 
 }  // namespace
 
-size_t list_lds_bytes(uint32_t n_sph, uint32_t n_node, uint32_t n_stack, bool *scene_in_lds) {
-    const size_t stacks = static_cast<size_t>(n_stack) * kBlock * sizeof(uint16_t);
-    const size_t scene = static_cast<size_t>(n_sph) * (2 * sizeof(float4) + sizeof(uint32_t)) +
-                         static_cast<size_t>(n_node) * rtw_accel::kNodeF4 * sizeof(float4);
-    *scene_in_lds = stacks + scene <= kListLdsCap;
-    return *scene_in_lds ? stacks + scene : (stacks ? stacks : 16);
-}
-
 hipError_t launch_accumulate_list(const ListParams &A_in, int n_cu, hipStream_t st, bool scene_lds) {
     ListParams A = A_in;
-    const FastParams &P = A.f;
     // entries a wave claims per cursor atomic: about 256 samples' worth, never more than 16
     A.chunk = std::min(16u, std::max(1u, 256u / std::max(A.m, 1u)));
-    hipError_t e = hipMemsetAsync(P.cursor, 0, sizeof(uint32_t), st);
-    if (e == hipSuccess) e = hipMemsetAsync(P.counters, 0, 6 * sizeof(unsigned long long), st);
-    if (e != hipSuccess) return e;
-    const uint64_t npix = static_cast<uint64_t>(P.n_rows) * P.W;
     // a wave starts on one pixel: no more workgroups than the shard could give work to
-    const uint32_t blocks = static_cast<uint32_t>(
-        std::min<uint64_t>(static_cast<uint64_t>(n_cu > 0 ? n_cu : 256) * 2, (npix + kWaves - 1) / kWaves));
-    bool in_lds = false;
-    size_t lds = list_lds_bytes(P.n_sph, P.n_node, P.n_stack, &in_lds);
-    if (!scene_lds && in_lds) {
-        in_lds = false;
-        lds = P.n_stack ? static_cast<size_t>(P.n_stack) * kBlock * sizeof(uint16_t) : 16;
-    }
-    if (in_lds) hipLaunchKernelGGL(rtw_fast_acc_list<true>, dim3(blocks), dim3(kBlock), lds, st, A);
-    else hipLaunchKernelGGL(rtw_fast_acc_list<false>, dim3(blocks), dim3(kBlock), lds, st, A);
-    return hipGetLastError();
+    return launch_persistent(rtw_fast_acc_list<true>, rtw_fast_acc_list<false>, A, A.f, false, 6, kWaves, kListLdsCap,
+                             n_cu, st, scene_lds);
 }
 
 hipError_t launch_resolve_counts(const unsigned long long *acc, const uint32_t *counts, uint64_t n_pixels,
@@ -374,23 +242,6 @@ hipError_t launch_resolve_counts(const unsigned long long *acc, const uint32_t *
 
 // ------------------------------------------------------------------- host ---
 namespace {
-
-#define HIPCHECK(expr)                                                                      \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess)                                                               \
-            throw rtw::Error(RTW_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-struct DeviceGuard {  // the caller's current device is restored on every exit
-    int dev = -1;
-    DeviceGuard() {
-        if (hipGetDevice(&dev) != hipSuccess) dev = -1;
-    }
-    ~DeviceGuard() {
-        if (dev >= 0) (void)hipSetDevice(dev);
-    }
-};
 
 // The selection's per-device scratch, grow-only, owned by the library: three bit planes
 // (u, n < N, listed) of one u64 per 64 pixels, and the per-wave counts / offsets.
@@ -474,14 +325,6 @@ int adaptive_select(int device, const uint32_t *counts, const unsigned long long
     HIPCHECK(hipEventRecord(c->ev_done, st));
     c->last_stream = st, c->pending = true;
     return RTW_OK;
-}
-
-uint32_t gcd_u32(uint32_t a, uint32_t b) {
-    while (b) {
-        const uint32_t t = a % b;
-        a = b, b = t;
-    }
-    return a;
 }
 
 }  // namespace
@@ -579,8 +422,8 @@ uint32_t rtw_lattice_stride(uint32_t N) {
     if (N <= 2) return 1;
     const double x = static_cast<double>(N) * ((std::sqrt(5.) - 1.) / 2.);
     uint32_t lo = static_cast<uint32_t>(x), hi = lo + 1;  // 1 <= lo < x < hi <= N - 1 ... both ends are coprime to N
-    while (gcd_u32(lo, N) != 1) --lo;
-    while (gcd_u32(hi, N) != 1) ++hi;
+    while (rtw::gcd_u32(lo, N) != 1) --lo;
+    while (rtw::gcd_u32(hi, N) != 1) ++hi;
     return x - static_cast<double>(lo) <= static_cast<double>(hi) - x ? lo : hi;
 }
 

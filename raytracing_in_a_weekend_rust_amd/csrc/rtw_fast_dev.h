@@ -1,7 +1,12 @@
-// rtw_fast_dev.h -- device code shared by the fast-mode kernels (rtw_fast.hip, the one-shot
-// render; rtw_fast_acc.hip, the progressive accumulate): random streams, get_ray, the
-// closest hit and the shading step. One definition, so a sample has the same bits in both.
+// rtw_fast_dev.h -- device code shared by every fast-mode kernel (rtw_fast.hip, the one-shot
+// render; rtw_fast_acc.hip, the progressive accumulate; rtw_fast_adapt.hip, the adaptive list
+// accumulate): random streams, get_ray, the closest hit, the shading step and the fixed-point
+// clamp, the staging of the scene into LDS, the ring scheduler of the three kernels that keep
+// a wave's pixels in a ring, the counters, the resolve of sums to a pixel, and the launch.
+// One definition of each, called and not copied, so a sample has the same bits on every route.
 #pragma once
+
+#include <algorithm>
 
 #include "rtw_accel.h"
 #include "rtw_capi.h"
@@ -11,7 +16,6 @@ namespace rtw_fast {
 namespace {
 
 constexpr uint32_t kWaves = kBlock / 64;
-constexpr uint32_t kRing = 4;
 constexpr uint32_t kFree = 0xffffffffu;
 
 struct Rng {
@@ -269,6 +273,238 @@ __device__ __forceinline__ bool trace_segment(const FastParams &P, const float4 
 // A finished sample's channel in the 32.32 fixed point of the pixel sums.
 __device__ __forceinline__ unsigned long long to_fixed(float c, float cmax) {
     return static_cast<unsigned long long>(fminf(fmaxf(c, 0.f), cmax) * 4294967296.f);  // 2^32
+}
+
+// Scene tables and the BVH into LDS behind the per-lane stacks.
+template <bool kLds>
+__device__ __forceinline__ void stage_scene(const FastParams &P, float4 *lds, uint32_t tid, const float4 *&geo,
+                                            const float4 *&mat, const float4 *&nodes, const uint32_t *&kind) {
+    geo = P.geo, mat = P.mat, nodes = P.nodes, kind = P.kind;
+    if constexpr (kLds) {
+        float4 *g = lds + P.n_stack * kBlock * sizeof(uint16_t) / sizeof(float4);
+        float4 *m = g + P.n_sph, *nd = m + P.n_sph;
+        uint32_t *kd = reinterpret_cast<uint32_t *>(nd + P.n_node * rtw_accel::kNodeF4);
+        for (uint32_t i = tid; i < P.n_sph; i += kBlock) g[i] = P.geo[i], m[i] = P.mat[i], kd[i] = P.kind[i];
+        for (uint32_t i = tid; i < P.n_node * rtw_accel::kNodeF4; i += kBlock) nd[i] = P.nodes[i];
+        geo = g, mat = m, nodes = nd, kind = kd;
+        __syncthreads();
+    }
+}
+
+__device__ __forceinline__ uint32_t rank_in(uint64_t mask) {  // set bits of mask below this lane
+    return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32),
+                                     __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0u));
+}
+
+// What a wave counted. segs, visits and wvisits are per lane; iters is wave-uniform.
+struct WaveStats {
+    uint32_t segs = 0, visits = 0, iters = 0, wvisits = 0;
+};
+
+// statistics: one atomic per wave and counter (FastParams::counters). done: the pixels that
+// need nothing more from this launch, per lane (per_lane) or wave-uniform already; traced: the
+// list kernel's samples ([5]; < 0: the launch has no such counter).
+__device__ __forceinline__ void add_counters(const FastParams &P, uint32_t lane, const WaveStats &w,
+                                             unsigned long long done, bool per_lane, long long traced = -1) {
+    unsigned long long sg = w.segs, vs = w.visits, wv = w.wvisits;
+    for (int o = 32; o > 0; o >>= 1) {
+        sg += __shfl_xor(sg, o);
+        vs += __shfl_xor(vs, o);
+        wv += __shfl_xor(wv, o);
+        if (per_lane) done += __shfl_xor(done, o);
+    }
+    if (lane == 0) {
+        atomicAdd(P.counters + 0, sg);
+        atomicAdd(P.counters + 1, vs);
+        atomicAdd(P.counters + 2, done);
+        atomicAdd(P.counters + 3, static_cast<unsigned long long>(w.iters));
+        atomicAdd(P.counters + 4, wv);
+        if (traced >= 0) atomicAdd(P.counters + 5, static_cast<unsigned long long>(traced));
+    }
+}
+
+// ---- the ring scheduler
+// A persistent wave keeps a ring of Use::kRing jobs in flight; a job is some samples of one
+// pixel. Idle lanes take the next samples of the newest job (ballot + mbcnt), so a lane whose
+// path ends starts another at once; a finished sample goes into the job's Use::kSums u64 sums
+// in LDS (LDS atomics: exact and order-free), and a job whose samples are all handed out and
+// back is flushed. The ring state (the jobs, their samples in flight, the job being handed
+// out and its next ordinal) is wave-uniform, in scalar registers. A Use says what differs:
+//   Job                   at least {pix}: the pixel, kFree in a free slot
+//   kRing, kSums          ring slots per wave, u64 sums per slot
+//   claim(lane, job)      the wave's next job from the launch's cursor: kJob, kSkip (the entry
+//                         needs nothing) or kDone (the cursor has passed the end)
+//   count(job)            its samples; lattice(job, i): the lattice sample k of its ordinal i
+//   add(sums, r, g, b)    a finished sample's 32.32 colour into a slot's sums
+//   flush(lane, job, sums)  the finished job's sums to global memory
+enum class Claim { kJob, kSkip, kDone };
+
+// The hand-out most kernels use: a wave claims `chunk` consecutive entries per cursor atomic
+// (every wave draws from one address, and its atomics serialise).
+struct ChunkCursor {
+    uint32_t at = 0, end = 0;  // the wave's entries claimed and not yet started
+    __device__ __forceinline__ bool next(const FastParams &P, uint32_t lane, uint32_t chunk, uint32_t n, uint32_t &e) {
+        if (at == end) {
+            uint32_t c = 0;
+            if (lane == 0) c = atomicAdd(P.cursor, chunk);
+            c = __builtin_amdgcn_readfirstlane(c);
+            if (c >= n) return false;
+            at = c, end = min(c + chunk, n);
+        }
+        e = at++;
+        return true;
+    }
+};
+
+// R, G, B sums: what a slot holds unless the Use adds to them.
+struct RgbSums {
+    static constexpr uint32_t kSums = 3;
+    static __device__ __forceinline__ void add(unsigned long long *a, unsigned long long r, unsigned long long g,
+                                               unsigned long long b) {
+        atomicAdd(a + 0, r);
+        atomicAdd(a + 1, g);
+        atomicAdd(a + 2, b);
+    }
+};
+
+// Runs the calling wave until the cursor is exhausted and its ring is empty; returns its
+// counts and, in flushed, the jobs it flushed. Every wave of the workgroup must call it.
+template <bool kLds, class Use>
+__device__ __forceinline__ WaveStats run_ring(const FastParams &P, Use &u, uint32_t &flushed) {
+    using Job = typename Use::Job;
+    constexpr uint32_t kRing = Use::kRing;
+    extern __shared__ __attribute__((aligned(16))) float4 lds[];
+    __shared__ unsigned long long acc[kWaves][kRing][Use::kSums];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    // per-lane stack column: slot j at stk[j * kBlock]
+    uint16_t *stk = reinterpret_cast<uint16_t *>(lds) + tid;
+    const float4 *geo, *mat, *nodes;
+    const uint32_t *kind;
+    stage_scene<kLds>(P, lds, tid, geo, mat, nodes, kind);
+    const float cmax = P.cmax;
+    // wave-uniform ring state
+    Job jobs[kRing], cur{};
+    uint32_t outst[kRing];
+#pragma unroll
+    for (uint32_t s = 0; s < kRing; ++s) jobs[s].pix = kFree, outst[s] = 0;
+    uint32_t cs = kFree, next = 0;
+    bool exhausted = false;
+    // lane path state
+    Seg g{};
+    float tr = 0.f, tg = 0.f, tb = 0.f;
+    uint32_t depth = 0, slot = kFree;
+    Rng rng{1u, 0u};
+    WaveStats w;
+    flushed = 0;
+    for (;;) {
+        // ---- hand out samples of the newest job to idle lanes
+        for (;;) {
+            const uint64_t need = __ballot(slot == kFree);
+            if (need == 0) break;
+            if (cs == kFree || next >= u.count(cur)) {
+                if (exhausted) break;
+                uint32_t f = kFree;
+#pragma unroll
+                for (uint32_t s = 0; s < kRing; ++s)
+                    if (f == kFree && jobs[s].pix == kFree) f = s;
+                if (f == kFree) break;
+                Job j;
+                const Claim c = u.claim(lane, j);
+                if (c == Claim::kDone) {
+                    exhausted = true;
+                    break;
+                }
+                if (c == Claim::kSkip) continue;
+#pragma unroll
+                for (uint32_t s = 0; s < kRing; ++s)
+                    if (s == f) jobs[s] = j, outst[s] = 0;
+                if (lane < Use::kSums) acc[wave][f][lane] = 0ull;
+                __builtin_amdgcn_wave_barrier();
+                cs = f, cur = j, next = 0;
+            }
+            const uint32_t rank = rank_in(need);
+            const uint32_t avail = u.count(cur) - next;
+            if (slot == kFree && rank < avail) {
+                start_path(P, cur.pix, u.lattice(cur, next + rank), rng, g);
+                tr = tg = tb = 1.f;
+                depth = 0;
+                slot = cs;
+            }
+            const uint32_t took = min(static_cast<uint32_t>(__builtin_popcountll(need)), avail);
+            next += took;
+#pragma unroll
+            for (uint32_t s = 0; s < kRing; ++s)
+                if (s == cs) outst[s] += took;
+        }
+        if (__ballot(slot != kFree) == 0) break;  // nothing handed out: the launch's work is done
+        ++w.iters;
+        // ---- one segment per busy lane; finished samples into their job's sums
+        float cr = 0.f, cg = 0.f, cb = 0.f;
+        const bool fin = slot != kFree && trace_segment(P, geo, mat, kind, nodes, g, rng, tr, tg, tb, depth, stk, w.segs,
+                                                        w.visits, w.wvisits, cr, cg, cb);
+        if (fin) Use::add(acc[wave][slot], to_fixed(cr, cmax), to_fixed(cg, cmax), to_fixed(cb, cmax));
+#pragma unroll
+        for (uint32_t s = 0; s < kRing; ++s)
+            outst[s] -= static_cast<uint32_t>(__builtin_popcountll(__ballot(fin && slot == s)));
+        if (fin) slot = kFree;
+        // ---- jobs whose samples are all handed out and finished
+#pragma unroll
+        for (uint32_t s = 0; s < kRing; ++s) {
+            if (jobs[s].pix != kFree && outst[s] == 0 && (s != cs || next >= u.count(cur))) {
+                __builtin_amdgcn_wave_barrier();
+                u.flush(lane, jobs[s], acc[wave][s]);
+                jobs[s].pix = kFree;
+                ++flushed;
+                if (s == cs) cs = kFree;
+            }
+        }
+    }
+    return w;
+}
+
+// ---- sums to images
+__device__ __forceinline__ uint32_t preview_u8(float mean) {  // Rust's `(mean as f64 * 255.) as u8`
+    const double v = static_cast<double>(mean) * 255.;
+    return v >= 255. ? 255u : (v > 0. ? static_cast<uint32_t>(v) : 0u);  // NaN -> 0
+}
+
+// A 32.32 sum over n samples to the f32 mean: an IEEE f64 divide, the same on every route.
+__device__ __forceinline__ float mean_f32(unsigned long long sum, double n) {
+    return static_cast<float>(static_cast<double>(sum) * (1. / 4294967296.) / n);
+}
+
+// Pixel p of the sums divided by n (0: the pixel resolves to 0) to the frame and/or the preview.
+__device__ __forceinline__ void resolve_pixel(const unsigned long long *__restrict__ acc, uint64_t p, double n,
+                                              float *__restrict__ out, uint32_t *__restrict__ preview) {
+    float m[3];
+#pragma unroll
+    for (uint32_t c = 0; c < 3; ++c) m[c] = n > 0. ? mean_f32(acc[p * 3u + c], n) : 0.f;
+    if (out) out[p * 3u + 0] = m[0], out[p * 3u + 1] = m[1], out[p * 3u + 2] = m[2];
+    if (preview) preview[p] = preview_u8(m[0]) | (preview_u8(m[1]) << 8) | (preview_u8(m[2]) << 16) | 0xff000000u;
+}
+
+// ---- the launch the persistent kernels share: the cursor and n_counters counters zeroed,
+// then (unless `nothing` is to be done) two workgroups per CU, no more than have work when a
+// workgroup starts on per_block pixels; the kernel with the scene in LDS when it fits below
+// cap and scene_lds allows it (A/B: RTW_FAST_LDS=0 under RTW_AB reads the scene from HBM).
+template <class Params>
+hipError_t launch_persistent(void (*in_lds_kernel)(Params), void (*global_kernel)(Params), const Params &A,
+                             const FastParams &P, bool nothing, uint32_t n_counters, uint64_t per_block, uint32_t cap,
+                             int n_cu, hipStream_t st, bool scene_lds) {
+    hipError_t e = hipMemsetAsync(P.cursor, 0, sizeof(uint32_t), st);
+    if (e == hipSuccess) e = hipMemsetAsync(P.counters, 0, n_counters * sizeof(unsigned long long), st);
+    if (e != hipSuccess || nothing) return e;
+    const uint64_t npix = static_cast<uint64_t>(P.n_rows) * P.W;
+    const uint32_t blocks = static_cast<uint32_t>(
+        std::min<uint64_t>(static_cast<uint64_t>(n_cu > 0 ? n_cu : 256) * 2, (npix + per_block - 1) / per_block));
+    bool in_lds = false;
+    size_t lds = lds_bytes(P.n_sph, P.n_node, P.n_stack, cap, &in_lds);
+    if (!scene_lds && in_lds) {
+        in_lds = false;
+        lds = P.n_stack ? static_cast<size_t>(P.n_stack) * kBlock * sizeof(uint16_t) : 16;
+    }
+    hipLaunchKernelGGL(in_lds ? in_lds_kernel : global_kernel, dim3(blocks), dim3(kBlock), lds, st, A);
+    return hipGetLastError();
 }
 
 }  // namespace

@@ -369,18 +369,6 @@ void render(rtw_group *g, const rtw_camera *cam, uint32_t samples_sqrt, rtw_u128
 
 }  // namespace
 
-// The caller's current device is restored on every exit of an rtw_group_* call
-// (the calls switch devices per entry; a torch caller's allocations must not move).
-struct DeviceGuard {
-    int dev = -1;
-    DeviceGuard() {
-        if (hipGetDevice(&dev) != hipSuccess) dev = -1;
-    }
-    ~DeviceGuard() {
-        if (dev >= 0) (void)hipSetDevice(dev);
-    }
-};
-
 #define RTW_GROUP_GUARD(body)                 \
     DeviceGuard device_guard_;                \
     try {                                     \

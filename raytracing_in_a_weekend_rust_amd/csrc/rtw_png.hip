@@ -640,23 +640,6 @@ __global__ __launch_bounds__(rtw::kPngScanBlock) void rtw_png_finish(const uint4
 }
 
 // ------------------------------------------------------------------- host ---
-#define HIPCHECK(expr)                                                                      \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess)                                                               \
-            throw rtw::Error(RTW_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-struct DeviceGuard {  // the caller's current device is restored on every exit
-    int dev = -1;
-    DeviceGuard() {
-        if (hipGetDevice(&dev) != hipSuccess) dev = -1;
-    }
-    ~DeviceGuard() {
-        if (dev >= 0) (void)hipSetDevice(dev);
-    }
-};
-
 // The fixed code-length code: complete (Kraft sum 1), short codes for what a sparse
 // length table is made of. Lengths by symbol 0..18: 0 and 18 take 3 bits, 17 and the
 // lengths 3..8 take 4, the rest 5.

@@ -272,23 +272,6 @@ __global__ __launch_bounds__(kPpmBlock) void rtw_ppm_emit(const uint8_t *__restr
 }
 
 // ------------------------------------------------------------------- host ---
-#define HIPCHECK(expr)                                                                      \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess)                                                               \
-            throw rtw::Error(RTW_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-struct DeviceGuard {  // the caller's current device is restored on every exit
-    int dev = -1;
-    DeviceGuard() {
-        if (hipGetDevice(&dev) != hipSuccess) dev = -1;
-    }
-    ~DeviceGuard() {
-        if (dev >= 0) (void)hipSetDevice(dev);
-    }
-};
-
 // Per-device scratch, grow-only, owned by the library.
 struct PpmCtx {
     int device = 0;

@@ -2456,13 +2456,6 @@ __global__ void probe_f64(const double *a, const double *b, uint64_t n, double *
 }
 
 // ------------------------------------------------------------------- host ---
-#define HIPCHECK(expr)                                                                   \
-    do {                                                                                 \
-        hipError_t e_ = (expr);                                                          \
-        if (e_ != hipSuccess)                                                            \
-            throw rtw::Error(RTW_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 uint32_t bit_length(uint64_t v) {
     uint32_t b = 0;
     while (v) ++b, v >>= 1;
@@ -3251,21 +3244,27 @@ void finish_fast(rtw_session *s, const rtw_fast::FastParams &F, uint64_t samples
     s->main_ev = true;
 }
 
-void render_fast(rtw_session *s, const rtw_camera *cam, uint32_t samples_sqrt, rtw_u128 seed,
-                 const rtw_shard *shard_in, float *out, hipStream_t stream) {
-    if (!cam || !out) throw rtw::Error(RTW_E_ARG, "null argument");
-    rtw_fast::FastParams F = fast_params(s, cam, samples_sqrt, seed, shard_in);
-    F.out = out;
-    hipStream_t st = stream;
+// Before a fast-mode launch on st: the session's device, the order after its last call and
+// the opening events. Returns whether the scene may be staged into LDS: always, but for
+// RTW_FAST_LDS=0 under RTW_AB (tuning is read only there, rtw_internal.h).
+bool begin_fast(rtw_session *s, hipStream_t st) {
     HIPCHECK(hipSetDevice(s->device));
     order_after_last(s, st);
     HIPCHECK(hipEventRecord(s->ev0, st));
     HIPCHECK(hipEventRecord(s->ev_k0, st));
-    const rtw::Knobs kn;  // tuning only under RTW_AB (rtw_internal.h)
-    const char *lds_knob = kn.get("RTW_FAST_LDS");
-    HIPCHECK(rtw_fast::launch(F, s->n_cu, st, !(lds_knob && !std::atoi(lds_knob))));
+    const char *lds_knob = rtw::Knobs().get("RTW_FAST_LDS");
+    return !(lds_knob && !std::atoi(lds_knob));
+}
+
+void render_fast(rtw_session *s, const rtw_camera *cam, uint32_t samples_sqrt, rtw_u128 seed,
+                 const rtw_shard *shard_in, float *out, hipStream_t st) {
+    if (!cam || !out) throw rtw::Error(RTW_E_ARG, "null argument");
+    rtw_fast::FastParams F = fast_params(s, cam, samples_sqrt, seed, shard_in);
+    F.out = out;
+    const bool scene_lds = begin_fast(s, st);
+    HIPCHECK(rtw_fast::launch(F, s->n_cu, st, scene_lds));
     bool in_lds = false;
-    finish_fast(s, F, F.n_off, static_cast<uint32_t>(rtw_fast::lds_bytes(F.n_sph, F.n_node, F.n_stack, &in_lds)), st);
+    finish_fast(s, F, F.n_off, static_cast<uint32_t>(rtw_fast::lds_bytes(F.n_sph, F.n_node, F.n_stack, rtw_fast::kLdsCap, &in_lds)), st);
 }
 
 // Progressive fast mode (rtw_fast_acc.hip): lattice samples k_first + i k_step, i < k_count,
@@ -3284,16 +3283,11 @@ void accumulate_fast(rtw_session *s, const rtw_camera *cam, uint32_t samples_sqr
         throw rtw::Error(RTW_E_UNSUPPORTED, "progressive fast mode: image too large");
     A.k_first = k_first, A.k_step = k_step, A.k_count = k_count;
     A.acc = acc;
-    HIPCHECK(hipSetDevice(s->device));
-    order_after_last(s, st);
-    HIPCHECK(hipEventRecord(s->ev0, st));
-    HIPCHECK(hipEventRecord(s->ev_k0, st));
-    const rtw::Knobs kn;  // tuning only under RTW_AB (rtw_internal.h)
-    const char *lds_knob = kn.get("RTW_FAST_LDS");
-    HIPCHECK(rtw_fast::launch_accumulate(A, s->n_cu, st, !(lds_knob && !std::atoi(lds_knob))));
+    const bool scene_lds = begin_fast(s, st);
+    HIPCHECK(rtw_fast::launch_accumulate(A, s->n_cu, st, scene_lds));
     if (k_count == 0) A.f.n_rows = 0;  // nothing launched, nothing flushed: the latch expects 0 pixels
     bool in_lds = false;
-    finish_fast(s, A.f, k_count, static_cast<uint32_t>(rtw_fast::acc_lds_bytes(A.f.n_sph, A.f.n_node, A.f.n_stack, &in_lds)), st);
+    finish_fast(s, A.f, k_count, static_cast<uint32_t>(rtw_fast::lds_bytes(A.f.n_sph, A.f.n_node, A.f.n_stack, rtw_fast::kAccLdsCap, &in_lds)), st);
 }
 
 // Adaptive fast mode (rtw_fast_adapt.hip): the next m samples, in the order i -> (i k_mul) mod N,
@@ -3308,27 +3302,17 @@ void accumulate_fast_list(rtw_session *s, const rtw_camera *cam, uint32_t sample
     rtw_fast::ListParams A{};
     A.f = fast_params(s, cam, samples_sqrt, seed, shard_in);
     if (A.f.n_off > 65535) throw rtw::Error(RTW_E_UNSUPPORTED, "adaptive fast mode: more than 65535 samples per pixel");
-    uint32_t a = k_mul, b = A.f.n_off;
-    while (b) {
-        const uint32_t t = a % b;
-        a = b, b = t;
-    }
-    if (a != 1) throw rtw::Error(RTW_E_ARG, "k_mul is not coprime to samples_sqrt^2");
+    if (rtw::gcd_u32(k_mul, A.f.n_off) != 1) throw rtw::Error(RTW_E_ARG, "k_mul is not coprime to samples_sqrt^2");
     // the entry cursor is 32 bits and every wave steps past the end once
     if (static_cast<uint64_t>(cam->img_height) * cam->img_width >= (1ull << 32) - (1u << 24))
         throw rtw::Error(RTW_E_UNSUPPORTED, "adaptive fast mode: image too large");
     A.list = list, A.n_list = n_list;
     A.m = m, A.k_mul = k_mul % A.f.n_off;  // the same order; the kernel's products stay below 2^32
     A.acc = acc, A.mom = mom, A.counts = counts;
-    HIPCHECK(hipSetDevice(s->device));
-    order_after_last(s, st);
-    HIPCHECK(hipEventRecord(s->ev0, st));
-    HIPCHECK(hipEventRecord(s->ev_k0, st));
-    const rtw::Knobs kn;  // tuning only under RTW_AB (rtw_internal.h)
-    const char *lds_knob = kn.get("RTW_FAST_LDS");
-    HIPCHECK(rtw_fast::launch_accumulate_list(A, s->n_cu, st, !(lds_knob && !std::atoi(lds_knob))));
+    const bool scene_lds = begin_fast(s, st);
+    HIPCHECK(rtw_fast::launch_accumulate_list(A, s->n_cu, st, scene_lds));
     bool in_lds = false;
-    finish_fast(s, A.f, 0, static_cast<uint32_t>(rtw_fast::list_lds_bytes(A.f.n_sph, A.f.n_node, A.f.n_stack, &in_lds)), st);
+    finish_fast(s, A.f, 0, static_cast<uint32_t>(rtw_fast::lds_bytes(A.f.n_sph, A.f.n_node, A.f.n_stack, rtw_fast::kListLdsCap, &in_lds)), st);
     s->last_list = true;
 }
 

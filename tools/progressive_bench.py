@@ -9,9 +9,9 @@ accumulate routes include zeroing the sums and the resolve. Cases:
   passes    s = 23 in 16, 64 and 529 strided passes, each followed by a resolve with both
             outputs, against render_fast; the median pass of the 529 is the preview's frame time
 Before a route is timed its final frame must be array_equal to the one-shot frame.
-One JSON line per case, printed and written to profiles/progressive/bench.jsonl.
+One JSON line per case, printed and written to --out.
 
-    python tools/progressive_bench.py [--reps 9] [--warmup 2] [--small]
+    python tools/progressive_bench.py [--reps 9] [--warmup 2] [--small] [--out FILE]
 """
 import argparse
 import json
@@ -34,6 +34,7 @@ def main():
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--small", action="store_true", help="a tiny image (a rehearsal of the script; nothing is written)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "progressive", "bench.jsonl"))
     a = ap.parse_args()
     h, w, big = (27, 48, 5) if a.small else (675, 1200, 23)
     cam, sph, n, mt, nm = rtw.builtin_scene("complex", SEED, h, w, 50)
@@ -110,9 +111,8 @@ def main():
         lines.append(line)
     sess.close()
     if not a.small:
-        out = os.path.join(ROOT, "profiles", "progressive")
-        os.makedirs(out, exist_ok=True)
-        with open(os.path.join(out, "bench.jsonl"), "w") as f:
+        os.makedirs(os.path.dirname(a.out), exist_ok=True)
+        with open(a.out, "w") as f:
             f.writelines(json.dumps(x) + "\n" for x in lines)
 
 
