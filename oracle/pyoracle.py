@@ -267,30 +267,41 @@ def scene_hit(objs, orig, d):  # hittable.rs:131-143, first minimum wins
     return best
 
 
-def reflectance(ir, cos):  # materials.rs:75-80, powi(5) = x * ((x*x) * (x*x))
-    r0 = (1.0 - ir) / (1.0 + ir)
-    r0 = r0 * r0
+def schlick(r0, cos):  # materials.rs:78-79, powi(5) = x * ((x*x) * (x*x))
     x = 1.0 - cos
     return r0 + (1.0 - r0) * (x * ((x * x) * (x * x)))
 
 
-def scatter(m, d, rec, rnd):  # materials.rs:22-37, 52-63, 83-111
+def reflectance(ir, cos):  # materials.rs:75-80
+    r0 = (1.0 - ir) / (1.0 + ir)
+    r0 = r0 * r0
+    return schlick(r0, cos)
+
+
+def scatter(m, d, rec, rnd, unit_vec=random_unit_vec, glass=None):
+    """materials.rs:22-37, 52-63, 83-111. unit_vec: the draw of a unit vector from rnd;
+    glass: (1/ir, ir, r0*r0) given ready-made instead of formed from ir here. Both are
+    for oracle/fast_model.py, which has other streams and f32-rounded constants; the
+    defaults are the reference's."""
     kind, albedo, fuzz, ir = m
     _, p, normal, front = rec
     if kind == LAMBERTIAN:
-        sd = add(normal, random_unit_vec(rnd))
+        sd = add(normal, unit_vec(rnd))
         if near_zero(sd):
             sd = normal
         return p, sd, albedo
     if kind == METAL:
         refl = reflect(unit(d), normal)
-        return p, add(refl, mul(random_unit_vec(rnd), fuzz)), albedo
-    ratio = 1.0 / ir if front else ir
+        return p, add(refl, mul(unit_vec(rnd), fuzz)), albedo
+    if glass is None:
+        ratio = 1.0 / ir if front else ir
+    else:
+        ratio = glass[0] if front else glass[1]
     ud = unit(d)
     cos_t = fmin(dot(neg(ud), normal), 1.0)
     sin_t = math.sqrt(1.0 - cos_t * cos_t)
     cant = ratio * sin_t > 1.0
-    if cant or reflectance(ir, cos_t) > rnd.next_01():
+    if cant or (reflectance(ir, cos_t) if glass is None else schlick(glass[2], cos_t)) > rnd.next_01():
         nd = reflect(ud, normal)
     else:
         nd = refract(ud, normal, ratio)
@@ -306,18 +317,24 @@ def ray_color(cam, objs, orig, d, rnd, depth, stats):  # camera.rs:376-398
         rec, m = hit
         o2, d2, att = scatter(m, d, rec, rnd)
         return mulv(att, ray_color(cam, objs, o2, d2, rnd, depth + 1, stats))
+    return sky(d)
+
+
+def sky(d):  # camera.rs:392-396
     ud = unit(d)
     a = 0.5 * (ud[1] + 1.0)
     return add(mul((1.0, 1.0, 1.0), 1.0 - a), mul((0.5, 0.7, 1.0), a))
 
 
-def get_ray(cam, i, j, offset, rnd):  # camera.rs:400-420, 452-456
+def get_ray(cam, i, j, offset, rnd, disk=random_vec_in_unit_disk):
+    """camera.rs:400-420, 452-456. disk: the draw of a point of the unit disk from rnd
+    (oracle/fast_model.py gives its own; the default is the reference's)."""
     loc = add(add(cam.pixel00, mul(cam.pixel_delta_u, float(i))), mul(cam.pixel_delta_v, float(j)))
     sample = add(loc, offset)
     if cam.defocus_angle <= 0.0:
         origin = cam.look_from
     else:
-        p = random_vec_in_unit_disk(rnd)
+        p = disk(rnd)
         origin = add(add(cam.look_from, mul(cam.defocus_disk_u, p[0])), mul(cam.defocus_disk_v, p[1]))
     return origin, sub(sample, origin)
 
