@@ -29,7 +29,7 @@ BUILD_ID := $(shell cat $(LIB_SRCS) | sha256sum | cut -c1-12)-$(shell echo '$(AR
 
 all: $(OUT)/librtw.so $(OUT)/rtw_cli oracle $(OUT)/accel_check $(OUT)/next01_check $(OUT)/try_check $(OUT)/karg_check.ok
 
-$(OUT)/rtw_render.o: $(SRC)/rtw_render.hip $(SRC)/rtw_fast.h $(SRC)/rtw_fast_adapt.h $(SRC)/rtw_accel.h $(SRC)/rtw_numeric.h $(SRC)/rtw_ppm.h include/rtw_capi.h $(SRC)/host/rtw_host.h $(SRC)/host/rtw_internal.h
+$(OUT)/rtw_render.o: $(SRC)/rtw_render.hip $(SRC)/rtw_fast.h $(SRC)/rtw_fast_adapt.h $(SRC)/rtw_fast_denoise.h $(SRC)/rtw_accel.h $(SRC)/rtw_numeric.h $(SRC)/rtw_ppm.h include/rtw_capi.h $(SRC)/host/rtw_host.h $(SRC)/host/rtw_internal.h
 	@mkdir -p $(OUT)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
@@ -47,6 +47,12 @@ $(OUT)/rtw_fast_acc.o: $(SRC)/rtw_fast_acc.hip $(SRC)/rtw_fast_dev.h $(SRC)/rtw_
 # adaptive fast mode: the list accumulate (the per-sample code of the two files above, so
 # their flags), the selection and the resolve by counts
 $(OUT)/rtw_fast_adapt.o: $(SRC)/rtw_fast_adapt.hip $(SRC)/rtw_fast_adapt.h $(SRC)/rtw_fast_dev.h $(SRC)/rtw_fast.h $(SRC)/rtw_accel.h $(SRC)/rtw_png.h include/rtw_capi.h $(SRC)/host/rtw_host.h $(SRC)/host/rtw_internal.h
+	@mkdir -p $(OUT)
+	$(HIPCC) $(filter-out -ffp-contract=off,$(HIPFLAGS)) -ffp-contract=fast -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
+
+# denoised fast mode: the first-hit guides (the closest hit of the files above, so their flags)
+# and the a-trous filter
+$(OUT)/rtw_fast_denoise.o: $(SRC)/rtw_fast_denoise.hip $(SRC)/rtw_fast_denoise.h $(SRC)/rtw_fast_dev.h $(SRC)/rtw_fast.h $(SRC)/rtw_accel.h include/rtw_capi.h $(SRC)/host/rtw_internal.h
 	@mkdir -p $(OUT)
 	$(HIPCC) $(filter-out -ffp-contract=off,$(HIPFLAGS)) -ffp-contract=fast -Xclang -target-feature -Xclang -packed-fp32-ops -c $< -o $@
 
@@ -96,7 +102,7 @@ $(OUT)/rtw_host.o: $(SRC)/host/rtw_host.cpp include/rtw_capi.h $(SRC)/host/rtw_h
 	@mkdir -p $(OUT)
 	$(CXX) $(CXXFLAGS) -I$(OUT) -c $< -o $@
 
-$(OUT)/librtw.so: $(OUT)/rtw_render.o $(OUT)/rtw_fast.o $(OUT)/rtw_fast_acc.o $(OUT)/rtw_fast_adapt.o $(OUT)/rtw_group.o $(OUT)/rtw_ppm.o $(OUT)/rtw_png.o $(OUT)/rtw_host.o $(OUT)/rtw_accel_build.o
+$(OUT)/librtw.so: $(OUT)/rtw_render.o $(OUT)/rtw_fast.o $(OUT)/rtw_fast_acc.o $(OUT)/rtw_fast_adapt.o $(OUT)/rtw_fast_denoise.o $(OUT)/rtw_group.o $(OUT)/rtw_ppm.o $(OUT)/rtw_png.o $(OUT)/rtw_host.o $(OUT)/rtw_accel_build.o
 	$(HIPCC) $(ARCHFLAGS) -shared -fPIC -o $@ $^ -Wl,-soname,librtw.so -lpthread -ldl
 
 $(OUT)/rtw_cli: $(SRC)/host/rtw_cli.cpp $(OUT)/librtw.so
@@ -113,10 +119,10 @@ $(OUT)/rtw_render_stamps.o: $(SRC)/rtw_render.hip include/rtw_capi.h $(SRC)/host
 # library must not report the default build's id)
 $(OUT)/rtw_host_stamps.o: $(SRC)/host/rtw_host.cpp include/rtw_capi.h $(SRC)/host/rtw_host.h $(SRC)/host/rtw_internal.h $(OUT)/rtw_build_id.h
 	$(CXX) $(CXXFLAGS) -I$(OUT) '-DRTW_BUILD_VARIANT="+stamps"' -c $< -o $@
-$(OUT)/librtw_stamps.so: $(OUT)/rtw_render_stamps.o $(OUT)/rtw_fast.o $(OUT)/rtw_fast_acc.o $(OUT)/rtw_fast_adapt.o $(OUT)/rtw_group.o $(OUT)/rtw_ppm.o $(OUT)/rtw_png.o $(OUT)/rtw_host_stamps.o $(OUT)/rtw_accel_build.o
+$(OUT)/librtw_stamps.so: $(OUT)/rtw_render_stamps.o $(OUT)/rtw_fast.o $(OUT)/rtw_fast_acc.o $(OUT)/rtw_fast_adapt.o $(OUT)/rtw_fast_denoise.o $(OUT)/rtw_group.o $(OUT)/rtw_ppm.o $(OUT)/rtw_png.o $(OUT)/rtw_host_stamps.o $(OUT)/rtw_accel_build.o
 	$(HIPCC) $(ARCHFLAGS) -shared -fPIC -o $@ $^ -Wl,-soname,librtw_stamps.so -lpthread
 
-RENDER_DEPS := $(SRC)/rtw_render.hip $(SRC)/rtw_fast.h $(SRC)/rtw_fast_adapt.h $(SRC)/rtw_accel.h $(SRC)/rtw_numeric.h $(SRC)/rtw_ppm.h include/rtw_capi.h $(SRC)/host/rtw_host.h $(SRC)/host/rtw_internal.h
+RENDER_DEPS := $(SRC)/rtw_render.hip $(SRC)/rtw_fast.h $(SRC)/rtw_fast_adapt.h $(SRC)/rtw_fast_denoise.h $(SRC)/rtw_accel.h $(SRC)/rtw_numeric.h $(SRC)/rtw_ppm.h include/rtw_capi.h $(SRC)/host/rtw_host.h $(SRC)/host/rtw_internal.h
 asm: build/rtw_render.s
 build/rtw_render.s: $(RENDER_DEPS)
 	@mkdir -p build

@@ -536,6 +536,81 @@ int rtw_session_render_fast_adaptive(rtw_session *s, const rtw_camera *cam, uint
                                      float *out_rgb_device, uint32_t *counts_out_device,
                                      void *hip_stream, rtw_adaptive_info *info);
 
+/* ---- denoised fast mode (ABI 7 additions) ----
+ * An edge-stopping a-trous filter of a fast-mode frame, driven by the frame's own variance
+ * (the adaptive buffers' counts and luminance moments) and by first-hit guides. The scene is
+ * spheres of one albedo each: on a sphere the normal determines the position, so there is no
+ * depth term, and equal tags mean equal albedo, so nothing is demodulated. What is seen through
+ * glass has no guide; Dielectric first hits pass through unfiltered by default. */
+
+/* Guides: one 16-byte record (nx, ny, nz, bits(tag)) per pixel of `shard` into guides_device
+ * (n_rows*W float4, 16-byte aligned, row-major like the frame), from the pixel-centre ray:
+ * rtw_session_render_fast's primary ray at samples_sqrt = 0, its origin look_from whatever
+ * defocus_angle is; nothing random. A hit (the fast-mode closest hit, t_min = 0.01 |d|) writes
+ * the shading normal (p - c)/r flipped to face the ray and tag = kind << 30 | sphere index
+ * (kinds RTW_LAMBERTIAN, RTW_METAL, RTW_DIELECTRIC = 0, 1, 2). A miss writes the unit ray
+ * direction, of which the sky's colour is a function, and tag = 0xffffffff.
+ * Asynchronous on hip_stream. Ordering, latch and errors as rtw_session_accumulate_fast;
+ * rtw_session_stats reports pixels, samples = segments = pixels and kernel_ms. A null
+ * guides_device is RTW_E_ARG; a scene of 2^30 spheres or more RTW_E_UNSUPPORTED. */
+int rtw_session_guides_fast(rtw_session *s, const rtw_camera *cam, const rtw_shard *shard,
+                            float *guides_device, void *hip_stream);
+
+typedef struct rtw_denoise_params {
+    uint32_t levels;       /* 0..8 a-trous levels, step 2^l; 0 = resolve only. default 5 */
+    uint32_t normal_log2;  /* 0..8: normal weight = max(0, n_p.n_q)^(2^normal_log2). default 5 */
+    uint32_t filter_mask;  /* bit kind (0,1,2) and bit 3 = sky: first-hit kinds that are filtered;
+                              other pixels pass through every level unchanged. default 0xB */
+    float    sigma_l;      /* luminance stop, in standard deviations of the mean. default 4 */
+} rtw_denoise_params;
+
+/* The filter over rows*width pixels, in f32. A pixel's kind is tag >> 30 (3: sky).
+ * Prepare. C0[p] = (r, g, b, v) with n = counts[p], A = mom[p][0], B = mom[p][1]:
+ *   r, g, b = (float)((double)acc * 2^-32 / (double)n), rtw_resolve_fast_counts's expression;
+ *   0 at n = 0. L = (r + g) + b. v, the variance of the mean of L:
+ *   n >= 2: D = n*B - A*A in unsigned 128-bit arithmetic (mod 2^128),
+ *           v = (float)((double)D * 2^-32 / ((double)n * (double)n * (double)(n-1))),
+ *           (double)D the nearest double; n = 1: v = L*L; n = 0: v = 0.
+ * Level l = 0 .. levels-1, C -> C'. Step t = 2^l, taps q = p + t*(i, j), i, j in -2..2, those
+ *   outside the buffer skipped; h = (1/16, 1/4, 3/8, 1/4, 1/16).
+ *   g_p = the (1,2,1)x(1,2,1) weighted mean of C[.].v over the in-buffer pixels p + t*(-1..1)^2,
+ *         normalised by the weights present;
+ *   w(p,q) = h_i h_j [tag_q == tag_p] max(0, n_p.n_q)^(2^normal_log2)
+ *            exp(-|L_p - L_q| / (sigma_l sqrt(g_p) + 1e-6)),
+ *         the power by normal_log2 squarings, the exponential as exp2 of the scaled argument;
+ *   C'[p].rgb = sum_q w C[q].rgb / sum_q w,  C'[p].v = sum_q w^2 C[q].v / (sum_q w)^2.
+ *   The centre tap goes through the same formula; the taps are summed j outer, i inner, so the
+ *   result is deterministic. A pixel whose kind's bit is not set in filter_mask: C'[p] = C[p].
+ * The last level (prepare when levels = 0) writes out_rgb_device (rows*width*3 f32), v to
+ * out_var_device (rows*width f32, nullable) and the RGBA8 preview of rtw_resolve_fast
+ * (nullable, 4-byte aligned). levels = 0 is rtw_resolve_fast_counts bit for bit. The frame
+ * feeds rtw_quantise_device, rtw_format_ppm_device and rtw_png_device like every fast frame.
+ * Asynchronous on hip_stream. Two float4 planes live in a per-device context the library owns
+ * (rtw_shutdown frees it); calls on one device are serialised and ordered on the device across
+ * streams, and the caller's current HIP device is restored. params NULL: the defaults.
+ * Errors, found before any device work: a null acc, counts, mom, guides or out_rgb; guides or
+ * mom not 16-byte aligned; levels > 8; normal_log2 > 8; filter_mask > 15; a negative or
+ * non-finite sigma_l: RTW_E_ARG. width or rows 0: RTW_E_EMPTY_IMAGE. 2^31 pixels or more:
+ * RTW_E_UNSUPPORTED. */
+int rtw_denoise_fast(int device, const unsigned long long *acc_device, const uint32_t *counts_device,
+                     const unsigned long long *mom_device, const float *guides_device,
+                     uint32_t width, uint32_t rows, const rtw_denoise_params *params,
+                     float *out_rgb_device, float *out_var_device, uint8_t *preview_rgba8_device,
+                     void *hip_stream);
+
+/* rtw_session_render_fast_adaptive's rounds (the same buffers, loop and info; tol_q16 = 0 is the
+ * uniform frame), then rtw_session_guides_fast and rtw_denoise_fast instead of the resolve by
+ * counts, into out_rgb_device and out_var_device (nullable). It blocks. *denoise_ms (nullable):
+ * the filter's kernels, from HIP events; the guides' time is rtw_session_stats' kernel_ms.
+ * Errors: both calls' and the adaptive driver's; a shard with row_step != 1 is RTW_E_ARG (the
+ * filter needs a pixel's neighbours in the buffer). */
+int rtw_session_render_fast_denoised(rtw_session *s, const rtw_camera *cam, uint32_t samples_sqrt,
+                                     rtw_u128 seed, const rtw_shard *shard, uint32_t tol_q16,
+                                     uint32_t floor_q16, uint32_t min_samples, uint32_t batch,
+                                     const rtw_denoise_params *params, float *out_rgb_device,
+                                     float *out_var_device, uint32_t *counts_out_device,
+                                     void *hip_stream, rtw_adaptive_info *info, double *denoise_ms);
+
 /* ---- device probes (tests) ---- */
 /* Device jump-ahead seeds (the kernel's own code path) for a pixel range. */
 int rtw_probe_device_seeds(int device, rtw_u128 seed, uint64_t first_pixel, uint64_t count,

@@ -115,6 +115,11 @@ class AdaptiveInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class DenoiseParams(C.Structure):
+    _fields_ = [("levels", C.c_uint32), ("normal_log2", C.c_uint32), ("filter_mask", C.c_uint32),
+                ("sigma_l", C.c_float)]
+
+
 GATHER_NAMES = {0: "none", 1: "copy", 2: "rccl"}
 FALLBACK_NAMES = {0: "none", 1: "rccl_unloadable", 2: "comm_init_failed"}
 GROUP_COPY_GATHER = 1
@@ -197,6 +202,13 @@ SIGNATURES = {
     "rtw_session_render_fast_adaptive": (C.c_int, [C.c_void_p, _P(Camera), C.c_uint32, U128, _P(Shard), C.c_uint32,
                                                    C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                                    C.c_void_p, _P(AdaptiveInfo)]),
+    "rtw_session_guides_fast": (C.c_int, [C.c_void_p, _P(Camera), _P(Shard), C.c_void_p, C.c_void_p]),
+    "rtw_denoise_fast": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                   _P(DenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "rtw_session_render_fast_denoised": (C.c_int, [C.c_void_p, _P(Camera), C.c_uint32, U128, _P(Shard), C.c_uint32,
+                                                   C.c_uint32, C.c_uint32, C.c_uint32, _P(DenoiseParams), C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, _P(AdaptiveInfo),
+                                                   _P(C.c_double)]),
     "rtw_session_stats": (C.c_int, [C.c_void_p, _P(Stats)]),
     "rtw_session_diag": (C.c_int, [C.c_void_p, _P(C.c_uint32), C.c_uint64]),
     "rtw_quantise_device": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p,

@@ -413,6 +413,20 @@ def resolve_fast_counts(acc_ptr: int, counts_ptr: int, shape, out_ptr: int = 0, 
                                       C.c_void_p(stream or 0)))
 
 
+def denoise_fast(acc_ptr: int, counts_ptr: int, mom_ptr: int, guides_ptr: int, shape, levels: int = 5,
+                 normal_log2: int = 5, filter_mask: int = 0xB, sigma_l: float = 4.0, out_ptr: int = 0, var_ptr: int = 0,
+                 preview_ptr: int = 0, device: int = 0, stream: int = 0):
+    """rtw_denoise_fast: the guided a-trous filter of the (rows, w) sums, counts, moments and
+    guides into the f32 frame at out_ptr, its variance plane at var_ptr and the RGBA8 preview at
+    preview_ptr (0: not wanted), asynchronously on `stream`. levels = 0 is resolve_fast_counts."""
+    h, w = shape
+    prm = capi.DenoiseParams(levels, normal_log2, filter_mask, sigma_l)
+    check(lib.rtw_denoise_fast(device, C.c_void_p(acc_ptr or None), C.c_void_p(counts_ptr or None),
+                               C.c_void_p(mom_ptr or None), C.c_void_p(guides_ptr or None), w, h, C.byref(prm),
+                               C.c_void_p(out_ptr or None), C.c_void_p(var_ptr or None),
+                               C.c_void_p(preview_ptr or None), C.c_void_p(stream or 0)))
+
+
 class Session:
     """Device-resident rendering (rtw_session_*): the scene lives in HBM; renders
     are enqueued on a caller HIP stream into a caller device buffer."""
@@ -483,6 +497,34 @@ class Session:
                                                    C.c_void_p(torch.cuda.current_stream().cuda_stream or 0),
                                                    C.byref(info)))
         return frame, counts, info.as_dict()
+
+    def guides_fast(self, cam: capi.Camera, guides_ptr: int, shard=None, stream: int = 0):
+        """rtw_session_guides_fast: (normal, bits(kind << 30 | sphere)) of every pixel's centre ray,
+        one float4 each, into the n_rows x W x 4 f32 buffer at guides_ptr."""
+        sh = _shard(shard)
+        check(lib.rtw_session_guides_fast(self.h, C.byref(cam), C.byref(sh) if sh is not None else None,
+                                          C.c_void_p(guides_ptr or None), C.c_void_p(stream or 0)))
+
+    def render_fast_denoised(self, cam: capi.Camera, samples_sqrt: int, seed: int, tol: float = 0.0,
+                             floor: float = 0.05, min_samples: int = 16, batch: int = 16, levels: int = 5,
+                             normal_log2: int = 5, filter_mask: int = 0xB, sigma_l: float = 4.0):
+        """rtw_session_render_fast_denoised (blocking): render_fast_adaptive's rounds (tol 0: the
+        uniform frame), then guides_fast and denoise_fast. Returns (frame f32 (h, w, 3), variance
+        f32 (h, w), counts int32 (h, w), info dict with denoise_ms), torch tensors."""
+        import torch
+        h, w = cam.img_height, cam.img_width
+        frame = torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
+        var = torch.empty((h, w), dtype=torch.float32, device="cuda")
+        counts = torch.empty((h, w), dtype=torch.int32, device="cuda")
+        info, ms = capi.AdaptiveInfo(), C.c_double()
+        prm = capi.DenoiseParams(levels, normal_log2, filter_mask, sigma_l)
+        check(lib.rtw_session_render_fast_denoised(self.h, C.byref(cam), samples_sqrt, capi.U128.of(seed), None,
+                                                   to_q16(tol, 65535), to_q16(floor, 1 << 24), min_samples, batch,
+                                                   C.byref(prm), C.c_void_p(frame.data_ptr()),
+                                                   C.c_void_p(var.data_ptr()), C.c_void_p(counts.data_ptr()),
+                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream or 0),
+                                                   C.byref(info), C.byref(ms)))
+        return frame, var, counts, dict(info.as_dict(), denoise_ms=ms.value)
 
     def progressive_fast(self, cam: capi.Camera, samples_sqrt: int, seed: int, passes: int):
         """Renders the lattice in `passes` strided passes (pass p: k = p mod passes) and

@@ -17,7 +17,9 @@
 // headless stand-in for the reference's preview window), --adaptive TOL (fast mode, one
 // device: every pixel sampled until the relative standard error of its mean is <= TOL or the
 // lattice is used up, rtw_session_render_fast_adaptive; --min-samples M and --batch B set the
-// first round's and the later rounds' samples per pixel). --preview is accepted and
+// first round's and the later rounds' samples per pixel), --denoise [LEVELS] (fast mode, one
+// device: the frame through the guided a-trous filter, rtw_session_render_fast_denoised; without
+// --adaptive at tolerance 0, so every pixel gets the whole lattice). --preview is accepted and
 // ignored: the winit window itself (application/mod.rs) is out of scope.
 #include <chrono>
 #include <cstdio>
@@ -44,6 +46,8 @@ struct Config {  // main.rs:13-29
     bool adaptive = false;
     double tol = 0.;
     uint32_t min_samples = 16, batch = 16;
+    bool denoise = false;
+    uint32_t levels = 5;
     std::vector<int> devices;  // empty: every visible device (--device-ppm: device 0)
 };
 
@@ -149,6 +153,11 @@ Config parse_args(int argc, char **argv) {
             }
             c.adaptive = true;
         }
+        else if (a == "--denoise") {  // the level count is optional
+            c.denoise = true;
+            uint32_t v = 0;
+            if (parse_u32(next, v)) c.levels = v;
+        }
         else if (a == "--min-samples") need(c.min_samples, "--min-samples");
         else if (a == "--batch") need(c.batch, "--batch");
         else if (a == "--help") {
@@ -170,6 +179,7 @@ Config parse_args(int argc, char **argv) {
             std::printf("\t--adaptive TOL\t:\tfast mode, one GPU: sample each pixel to a relative standard error of TOL\n");
             std::printf("\t--min-samples M\t:\twith --adaptive: samples every pixel gets first (default 16)\n");
             std::printf("\t--batch B\t:\twith --adaptive: samples per listed pixel and round (default 16)\n");
+            std::printf("\t--denoise [L]\t:\tfast mode, one GPU: filter the frame with L a-trous levels (default 5)\n");
             std::exit(0);
         }
     }
@@ -180,6 +190,10 @@ Config parse_args(int argc, char **argv) {
     }
     if (c.adaptive && (!c.fast || c.passes || c.devices.size() > 1)) {
         std::fprintf(stderr, "--adaptive needs --mode fast on one device, without --passes\n");
+        std::exit(1);
+    }
+    if (c.denoise && (!c.fast || c.passes || c.devices.size() > 1)) {
+        std::fprintf(stderr, "--denoise needs --mode fast on one device, without --passes\n");
         std::exit(1);
     }
     if ((c.device_ppm || c.png) && c.devices.size() > 1) {  // the frame of a multi-device render is gathered on the host
@@ -219,12 +233,16 @@ int main(int argc, char **argv) {
             b.cam.width(), b.cam.height(), cfg.sample_sqrt * cfg.sample_sqrt, b.cam.d.max_depth);
         rtw_stats st{};
         const auto t0 = std::chrono::steady_clock::now();
-        if (cfg.adaptive) {
+        if (cfg.adaptive || cfg.denoise) {
             std::vector<float> f32;
             rtw_adaptive_info info{};
+            const rtw_denoise_params dn{cfg.levels, 5u, 0xBu, 4.f};
+            double denoise_ms = 0.;
             const std::string file = rtw::render_adaptive_device(
                 b.cam, *b.world, cfg.sample_sqrt, seed, cfg.devices.empty() ? 0 : cfg.devices[0], cfg.tol, 0.05,
-                cfg.min_samples, cfg.batch, cfg.png ? 2 : (cfg.device_ppm ? 1 : 0), &f32, &info, &st);
+                cfg.min_samples, cfg.batch, cfg.png ? 2 : (cfg.device_ppm ? 1 : 0), &f32, &info, &st,
+                cfg.denoise ? &dn : nullptr, &denoise_ms);
+            if (cfg.denoise) std::printf("denoise: %u levels, filter %.3f ms\n", cfg.levels, denoise_ms);
             std::printf("adaptive: %u rounds, %llu samples, %.2f mean samples per pixel\n", info.rounds,
                         static_cast<unsigned long long>(info.samples),
                         static_cast<double>(info.samples) / static_cast<double>(st.pixels ? st.pixels : 1));

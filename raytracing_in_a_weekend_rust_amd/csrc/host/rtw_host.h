@@ -204,10 +204,12 @@ std::string render_progressive_device(const Camera &cam, const Scene &world, uin
 
 // rtw_cli --mode fast --adaptive TOL: rtw_session_render_fast_adaptive on one device.
 // output 0: *frame gets the f32 frame; 1: returns the PPM text made on the device
-// (rtw_format_ppm_device); 2: returns the PNG file (rtw_png_device). Throws on error.
+// (rtw_format_ppm_device); 2: returns the PNG file (rtw_png_device). denoise (--denoise): the
+// frame is rtw_session_render_fast_denoised's, *denoise_ms its filter time. Throws on error.
 std::string render_adaptive_device(const Camera &cam, const Scene &world, uint32_t samples_sqrt, rtw_u128 seed,
                                    int device, double tol, double floor, uint32_t min_samples, uint32_t batch, int output,
-                                   std::vector<float> *frame, rtw_adaptive_info *info, rtw_stats *stats);
+                                   std::vector<float> *frame, rtw_adaptive_info *info, rtw_stats *stats,
+                                   const rtw_denoise_params *denoise = nullptr, double *denoise_ms = nullptr);
 // A tolerance or luminance floor as a fraction to its q16 argument: round(v * 65536)
 // clamped to [0, max] (the Python binding's rule, api.py to_q16).
 uint32_t tol_to_q16(double v, uint32_t max);

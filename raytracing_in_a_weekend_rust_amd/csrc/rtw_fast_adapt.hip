@@ -346,7 +346,8 @@ uint32_t tol_to_q16(double v, uint32_t max) {
 
 std::string render_adaptive_device(const Camera &cam, const Scene &world, uint32_t samples_sqrt, rtw_u128 seed,
                                    int device, double tol, double floor, uint32_t min_samples, uint32_t batch, int output,
-                                   std::vector<float> *frame, rtw_adaptive_info *info, rtw_stats *stats) {
+                                   std::vector<float> *frame, rtw_adaptive_info *info, rtw_stats *stats,
+                                   const rtw_denoise_params *denoise, double *denoise_ms) {
     DeviceGuard guard;
     FlatScene flat;
     world.flatten(flat);
@@ -364,9 +365,14 @@ std::string render_adaptive_device(const Camera &cam, const Scene &world, uint32
         const uint64_t n = std::max<uint64_t>(static_cast<uint64_t>(w) * h * 3, 1);
         HIPCHECK(hipSetDevice(device));
         HIPCHECK(hipMalloc(&d_fb, n * sizeof(float)));
-        ok(rtw_session_render_fast_adaptive(s, &cam.d, samples_sqrt, seed, nullptr, tol_to_q16(tol, 65535u),
-                                            tol_to_q16(floor, 1u << 24), min_samples, batch, static_cast<float *>(d_fb),
-                                            nullptr, nullptr, info));
+        if (denoise)
+            ok(rtw_session_render_fast_denoised(s, &cam.d, samples_sqrt, seed, nullptr, tol_to_q16(tol, 65535u),
+                                                tol_to_q16(floor, 1u << 24), min_samples, batch, denoise,
+                                                static_cast<float *>(d_fb), nullptr, nullptr, nullptr, info, denoise_ms));
+        else
+            ok(rtw_session_render_fast_adaptive(s, &cam.d, samples_sqrt, seed, nullptr, tol_to_q16(tol, 65535u),
+                                                tol_to_q16(floor, 1u << 24), min_samples, batch,
+                                                static_cast<float *>(d_fb), nullptr, nullptr, info));
         if (stats) {  // the driver's totals in the shape the one-shot renders report
             *stats = rtw_stats{};
             stats->pixels = static_cast<uint64_t>(w) * h;

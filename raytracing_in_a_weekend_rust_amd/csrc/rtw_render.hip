@@ -45,6 +45,7 @@
 #include "rtw_capi.h"
 #include "rtw_fast.h"
 #include "rtw_fast_adapt.h"
+#include "rtw_fast_denoise.h"
 #include "rtw_numeric.h"
 #include "rtw_ppm.h"
 #include "host/rtw_host.h"
@@ -2516,6 +2517,8 @@ struct rtw_session {
     uint32_t *d_acounts = nullptr, *d_alist = nullptr, *d_an = nullptr;
     unsigned long long *h_an = nullptr;
     size_t adapt_cap = 0;
+    float4 *d_aguides = nullptr;  // the denoised driver's guides (grow-only)
+    size_t guides_cap = 0;
     hipEvent_t ev_s0 = nullptr, ev_s1 = nullptr;  // around a selection
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr;  // around the main kernel (rtw_stats.main_kernel_ms)
@@ -3319,18 +3322,40 @@ void accumulate_fast_list(rtw_session *s, const rtw_camera *cam, uint32_t sample
 void check_latch(rtw_session *s);
 void collect(rtw_session *s);
 
-// The adaptive driver: rounds of accumulate_fast_list and rtw_adaptive_select on buffers the
-// session owns, until no pixel is listed; it waits for each round's list length.
+// First-hit guides (rtw_fast_denoise.hip): the fast-mode launch at samples_sqrt = 0 without
+// defocus, i.e. start_path's pixel-centre ray from look_from.
+void guides_fast(rtw_session *s, const rtw_camera *cam, const rtw_shard *shard_in, float *guides, hipStream_t st) {
+    if (!cam || !guides) throw rtw::Error(RTW_E_ARG, "null argument");
+    if (reinterpret_cast<uintptr_t>(guides) % 16) throw rtw::Error(RTW_E_ARG, "guides buffer not 16-byte aligned");
+    rtw_fast::GuideParams A{};
+    A.f = fast_params(s, cam, 0, rtw_u128{0, 0}, shard_in);
+    if (s->n_sph >= (1u << 30)) throw rtw::Error(RTW_E_UNSUPPORTED, "guides: 2^30 spheres or more");
+    A.f.defocus = 0;
+    A.guides = reinterpret_cast<float4 *>(guides);
+    A.tiles_x = (A.f.W + 7u) / 8u;
+    A.n_tiles = A.tiles_x * ((A.f.n_rows + 7u) / 8u);
+    const bool scene_lds = begin_fast(s, st);
+    HIPCHECK(rtw_fast::launch_guides(A, s->n_cu, st, scene_lds));
+    bool in_lds = false;
+    finish_fast(s, A.f, 1, static_cast<uint32_t>(rtw_fast::lds_bytes(A.f.n_sph, A.f.n_node, A.f.n_stack, rtw_fast::kLdsCap, &in_lds)), st);
+}
+
+// The adaptive drivers: rounds of accumulate_fast_list and rtw_adaptive_select on buffers the
+// session owns, until no pixel is listed; it waits for each round's list length. Then the
+// resolve by counts (dn null), or the guides and the filter (rtw_session_render_fast_denoised).
 void render_fast_adaptive(rtw_session *s, const rtw_camera *cam, uint32_t samples_sqrt, rtw_u128 seed,
                           const rtw_shard *shard_in, uint32_t tol_q16, uint32_t floor_q16, uint32_t min_samples,
-                          uint32_t batch, float *out, uint32_t *counts_out, hipStream_t st, rtw_adaptive_info *info) {
+                          uint32_t batch, float *out, uint32_t *counts_out, hipStream_t st, rtw_adaptive_info *info,
+                          const rtw_denoise_params *dn = nullptr, float *out_var = nullptr, double *denoise_ms = nullptr) {
     if (!cam || !out) throw rtw::Error(RTW_E_ARG, "null argument");
     if (batch == 0 || batch > 65535) throw rtw::Error(RTW_E_ARG, "batch outside 1..65535");
     if (tol_q16 > 65535u || floor_q16 > (1u << 24)) throw rtw::Error(RTW_E_ARG, "tol_q16 > 65535 or floor_q16 > 2^24");
     const rtw_fast::FastParams F = fast_params(s, cam, samples_sqrt, seed, shard_in);  // the checks, and the shard
     const uint32_t N = F.n_off;
     if (N > 65535) throw rtw::Error(RTW_E_UNSUPPORTED, "adaptive fast mode: more than 65535 samples per pixel");
+    if (dn && F.row_step != 1) throw rtw::Error(RTW_E_ARG, "denoise: a shard with row_step != 1");
     const size_t npix = static_cast<size_t>(F.n_rows) * F.W;
+    if (dn && npix >= (1ull << 31)) throw rtw::Error(RTW_E_UNSUPPORTED, "denoise: image of 2^31 pixels or more");
     rtw_adaptive_info I{};
     HIPCHECK(hipSetDevice(s->device));
     if (!s->h_an) {
@@ -3377,12 +3402,34 @@ void render_fast_adaptive(rtw_session *s, const rtw_camera *cam, uint32_t sample
             if (*reinterpret_cast<const uint32_t *>(s->h_an) == 0) break;
             round(s->d_alist, batch);
         }
-        HIPCHECK(rtw_fast::launch_resolve_counts(s->d_aacc, s->d_acounts, npix, out, nullptr, N, s->d_afull, st));
+        // the resolve by counts; with the filter it only counts the pixels at the lattice's end
+        HIPCHECK(rtw_fast::launch_resolve_counts(s->d_aacc, s->d_acounts, npix, dn ? nullptr : out, nullptr, N, s->d_afull, st));
+        if (dn) {
+            if (npix > s->guides_cap) {
+                dev_free(s->d_aguides);
+                s->d_aguides = nullptr, s->guides_cap = 0;
+                HIPCHECK(hipMalloc(&s->d_aguides, npix * sizeof(float4)));
+                s->guides_cap = npix;
+            }
+            guides_fast(s, cam, shard_in, reinterpret_cast<float *>(s->d_aguides), st);
+            HIPCHECK(hipEventRecord(s->ev_s0, st));
+            const int rc = rtw_denoise_fast(s->device, s->d_aacc, s->d_acounts, s->d_amom, reinterpret_cast<const float *>(s->d_aguides),
+                                            F.W, F.n_rows, dn, out, out_var, nullptr, st);
+            if (rc != RTW_OK) throw rtw::Error(rc, rtw::last_error());
+            HIPCHECK(hipEventRecord(s->ev_s1, st));
+        }
         if (counts_out)
             HIPCHECK(hipMemcpyAsync(counts_out, s->d_acounts, npix * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
         HIPCHECK(hipMemcpyAsync(s->h_an + 1, s->d_afull, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         HIPCHECK(hipStreamSynchronize(st));
         I.pixels_full = s->h_an[1];
+        if (dn && denoise_ms) {
+            float ms = 0.f;
+            HIPCHECK(hipEventElapsedTime(&ms, s->ev_s0, s->ev_s1));
+            *denoise_ms = ms;
+        }
+    } else if (denoise_ms) {
+        *denoise_ms = 0.;
     }
     if (info) *info = I;
 }
@@ -3642,7 +3689,7 @@ int rtw_session_destroy(rtw_session *s) {
     dev_free(s->d_pcost), dev_free(s->d_err);
     dev_free(s->d_fcursor), dev_free(s->d_fcount);
     dev_free(s->d_aacc), dev_free(s->d_amom), dev_free(s->d_afull), dev_free(s->d_acounts), dev_free(s->d_alist);
-    dev_free(s->d_an);
+    dev_free(s->d_an), dev_free(s->d_aguides);
     if (s->h_an) (void)hipHostFree(s->h_an);
     if (s->ev_s0) (void)hipEventDestroy(s->ev_s0);
     if (s->ev_s1) (void)hipEventDestroy(s->ev_s1);
@@ -3737,6 +3784,29 @@ int rtw_session_render_fast_adaptive(rtw_session *s, const rtw_camera *cam, uint
     RTW_GUARD_END
 }
 
+int rtw_session_guides_fast(rtw_session *s, const rtw_camera *cam, const rtw_shard *shard, float *guides_device,
+                            void *hip_stream) {
+    if (!s) return rtw::set_error("null session"), RTW_E_ARG;
+    RTW_GUARD_BEGIN
+    guides_fast(s, cam, shard, guides_device, static_cast<hipStream_t>(hip_stream));
+    return RTW_OK;
+    RTW_GUARD_END
+}
+
+int rtw_session_render_fast_denoised(rtw_session *s, const rtw_camera *cam, uint32_t samples_sqrt, rtw_u128 seed,
+                                     const rtw_shard *shard, uint32_t tol_q16, uint32_t floor_q16, uint32_t min_samples,
+                                     uint32_t batch, const rtw_denoise_params *params, float *out_rgb_device,
+                                     float *out_var_device, uint32_t *counts_out_device, void *hip_stream,
+                                     rtw_adaptive_info *info, double *denoise_ms) {
+    if (!s) return rtw::set_error("null session"), RTW_E_ARG;
+    RTW_GUARD_BEGIN
+    const rtw_denoise_params dn = rtw::checked_denoise_params(params);
+    render_fast_adaptive(s, cam, samples_sqrt, seed, shard, tol_q16, floor_q16, min_samples, batch, out_rgb_device,
+                         counts_out_device, static_cast<hipStream_t>(hip_stream), info, &dn, out_var_device, denoise_ms);
+    return RTW_OK;
+    RTW_GUARD_END
+}
+
 int rtw_session_stats(rtw_session *s, rtw_stats *out) {
     if (!s || !out) return rtw::set_error("null argument"), RTW_E_ARG;
     RTW_GUARD_BEGIN
@@ -3795,6 +3865,7 @@ int rtw_shutdown(void) {
     g_multi.clear();
     rtw::ppm_shutdown();  // the device output stage's per-device contexts (rtw_ppm.hip)
     rtw::adapt_shutdown();  // the adaptive selection's (rtw_fast_adapt.hip)
+    rtw::denoise_shutdown();  // the filter's planes (rtw_fast_denoise.hip)
     return RTW_OK;
 }
 
