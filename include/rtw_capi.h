@@ -160,7 +160,8 @@ int rtw_seed_children(rtw_u128 seed, uint64_t first_pixel, uint64_t count, rtw_u
  * "three_lambertian" (BASELINE config 1: simple() with the dielectric dropped and
  * the metal sphere made Lambertian). img_height/img_width/max_depth override the
  * builder's hard-coded values when non-zero. Writes up to `cap` spheres and
- * materials; *n_spheres / *n_mats receive the full counts. */
+ * materials; *n_spheres / *n_mats receive the full counts. "bouncing" is RTW_E_ARG here:
+ * that scene moves, and rtw_scene_bouncing returns it with its second centres. */
 int rtw_scene_builtin(const char *name, rtw_u128 seed, uint32_t img_height, uint32_t img_width,
                       uint32_t max_depth, rtw_camera *cam, rtw_sphere *spheres,
                       rtw_material *mats, uint32_t cap, uint32_t *n_spheres, uint32_t *n_mats);
@@ -610,6 +611,53 @@ int rtw_session_render_fast_denoised(rtw_session *s, const rtw_camera *cam, uint
                                      const rtw_denoise_params *params, float *out_rgb_device,
                                      float *out_var_device, uint32_t *counts_out_device,
                                      void *hip_stream, rtw_adaptive_info *info, double *denoise_ms);
+
+/* ---- motion blur in fast mode (ABI 7 additions) ----
+ * Spheres that move in a straight line while the shutter is open, t in [0, 1). Every sample has
+ * a time of its own, and a sample at time t sees static spheres at c(t). f64 parity mode has no
+ * motion (the reference has none to be bit-exact against). */
+
+/* rtw_session_set_scene with a second centre per sphere. center1: n_spheres*3 doubles; sphere i is
+ * at spheres[i].center at time 0 and at center1[i] at time 1, its radius constant. With
+ * c0 = f32(center0) and v = f32(center1 - center0) (the difference in f64, then rounded), the
+ * sphere at time t is c(t) = fmaf(t, v, c0) per component, the same expression in the closest
+ * hit and in the shading normal. A sphere moves if any component of its v is not zero. If
+ * center1 is NULL or no sphere moves, the call is rtw_session_set_scene: the same tables, kernels
+ * and bits. A later rtw_session_set_scene makes the session static again. Limits and validation
+ * are rtw_session_set_scene's.
+ * On a moving scene rtw_session_render_fast, rtw_session_accumulate_fast,
+ * rtw_session_accumulate_fast_list and rtw_session_render_fast_adaptive work as on a static one,
+ * and every split of the lattice still adds up to rtw_session_render_fast's frame bit for bit.
+ * rtw_session_render, rtw_session_guides_fast and rtw_session_render_fast_denoised return
+ * RTW_E_UNSUPPORTED before any device work (a first hit at one instant is no guide for a blurred
+ * pixel). Groups and the rtw_threaded_render* one-shots take static scenes only. */
+int rtw_session_set_scene_moving(rtw_session *s, const rtw_sphere *spheres, uint32_t n_spheres,
+                                 const double *center1, const rtw_material *mats, uint32_t n_mats);
+
+/* The time of lattice sample k (k < N) of a pixel, in units of 2^-24: t = T24 * 2^-24, exact in
+ * f32. A pure function of its arguments that takes nothing from the sample's random stream. With
+ * N = max(1, samples_sqrt^2) (an N of 0 is read as 1), g = rtw_lattice_stride(N), global_pixel =
+ * y*W + x of the whole image and seed_mix = seed.lo ^ seed.hi*0x9e3779b97f4a7c15 (mod 2^64):
+ *   j    = (k*g) mod N, the product in 64 bits: a bijection, and (k, j) is a rank-1 lattice, so
+ *          time does not line up with the sub-pixel row as k/N would;
+ *   base = floor((2j + 1) * 2^23 / N);
+ *   H    = fmix64(fmix64(seed_mix ^ global_pixel*0x9e3779b97f4a7c15) + 2^32) >> 40, fmix64
+ *          SplitMix64's finaliser; the inner hash is the streams' own, whose k < 2^32 never
+ *          reaches the added constant;
+ *   T24  = (base + H) mod 2^24.
+ * A pixel's N times fall one in each stratum [i/N, (i+1)/N) of [0, 1) rotated by H, so
+ * neighbouring pixels show noise and not N shared ghost images. Host only, needs no GPU. */
+uint32_t rtw_fast_sample_time(rtw_u128 seed, uint64_t global_pixel, uint32_t k, uint32_t N);
+
+/* The "bouncing" scene: rtw_scene_builtin("complex", seed, ...) bit for bit (camera, spheres,
+ * materials, order), and for every sphere a row of center1 (cap*3 doubles, nullable):
+ * center1 = center0 + (0, 0.5*u, 0) for each small (radius 0.2) Lambertian sphere, center0 for
+ * every other. The u are next_01 draws, in sphere order, of an XorShift of their own whose state
+ * is seed with 0x626f756e63696e67 ("bouncing") xored into its low half; complex's own draws are
+ * not disturbed. Counts, capacity and errors as rtw_scene_builtin. */
+int rtw_scene_bouncing(rtw_u128 seed, uint32_t img_height, uint32_t img_width, uint32_t max_depth,
+                       rtw_camera *cam, rtw_sphere *spheres, double *center1, rtw_material *mats,
+                       uint32_t cap, uint32_t *n_spheres, uint32_t *n_mats);
 
 /* ---- device probes (tests) ---- */
 /* Device jump-ahead seeds (the kernel's own code path) for a pixel range. */

@@ -183,6 +183,11 @@ SIGNATURES = {
     "rtw_session_destroy": (C.c_int, [C.c_void_p]),
     "rtw_session_set_scene": (C.c_int, [C.c_void_p, _P(Sphere), C.c_uint32, _P(Material),
                                         C.c_uint32]),
+    "rtw_session_set_scene_moving": (C.c_int, [C.c_void_p, _P(Sphere), C.c_uint32, _P(C.c_double), _P(Material),
+                                               C.c_uint32]),
+    "rtw_fast_sample_time": (C.c_uint32, [U128, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "rtw_scene_bouncing": (C.c_int, [U128, C.c_uint32, C.c_uint32, C.c_uint32, _P(Camera), _P(Sphere),
+                                     _P(C.c_double), _P(Material), C.c_uint32, _P(C.c_uint32), _P(C.c_uint32)]),
     "rtw_session_render": (C.c_int, [C.c_void_p, _P(Camera), C.c_uint32, U128, _P(Shard),
                                      C.c_void_p, C.c_void_p]),
     "rtw_session_render_fast": (C.c_int, [C.c_void_p, _P(Camera), C.c_uint32, U128, _P(Shard),

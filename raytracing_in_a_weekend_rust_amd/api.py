@@ -79,10 +79,16 @@ class Sphere:  # sphere.rs:11-37
     center: tuple
     radius: float
     mat: Material
+    center1: tuple | None = None  # at time 1 (fast-mode motion blur); None: the sphere stands still
 
     @staticmethod
     def new_world_obj(x, y, z, radius, mat) -> "Sphere":
         return Sphere((x, y, z), radius, mat)
+
+    @staticmethod
+    def new_moving_world_obj(c0, c1, radius, mat) -> "Sphere":
+        """The book's moving sphere: at c0 when the shutter opens (t = 0), at c1 when it closes."""
+        return Sphere(tuple(c0), radius, mat, tuple(c1))
 
 
 @dataclass(eq=False)
@@ -105,6 +111,15 @@ class Scene:  # hittable.rs:119-143
             s.mat = index[id(o.mat)]
         mt = (capi.Material * max(1, len(mats)))(*mats)
         return sph, len(self.objects), mt, len(mats)
+
+    def flatten_moving(self):
+        """flatten() with center1 after the spheres' count, as Session.set_scene_moving takes it:
+        3 doubles per sphere, its centre at time 1 (its centre for a sphere that stands still)."""
+        sph, n, mt, nm = self.flatten()
+        c1 = (C.c_double * max(3, 3 * n))()
+        for i, o in enumerate(self.objects):
+            c1[3 * i:3 * i + 3] = [float(c) for c in (o.center if o.center1 is None else o.center1)]
+        return sph, n, c1, mt, nm
 
 
 class SceneBuilder:  # hittable.rs:86-117
@@ -180,6 +195,26 @@ def builtin_scene(name: str, seed: int = DEFAULT_SEED, height=0, width=0, max_de
     check(lib.rtw_scene_builtin(name.encode(), capi.U128.of(seed), height, width, max_depth,
                                 C.byref(cam), sph, mt, cap, C.byref(ns), C.byref(nm)))
     return Camera(cam), sph, ns.value, mt, nm.value
+
+
+def bouncing_scene(seed: int = DEFAULT_SEED, height=0, width=0, max_depth=0):
+    """rtw_scene_bouncing: builtin_scene("complex") with its small Lambertian spheres moving up
+    while the shutter is open: (Camera, spheres, n, center1, mats, nm) for Session.set_scene_moving."""
+    ns, nm = C.c_uint32(), C.c_uint32()
+    cam, args = capi.Camera(), (capi.U128.of(seed), height, width, max_depth)
+    rc = lib.rtw_scene_bouncing(*args, C.byref(cam), None, None, None, 0, C.byref(ns), C.byref(nm))
+    if rc not in (0, -8):
+        check(rc)
+    cap = max(ns.value, nm.value, 1)
+    sph, mt, c1 = (capi.Sphere * cap)(), (capi.Material * cap)(), (C.c_double * (3 * cap))()
+    check(lib.rtw_scene_bouncing(*args, C.byref(cam), sph, c1, mt, cap, C.byref(ns), C.byref(nm)))
+    return Camera(cam), sph, ns.value, c1, mt, nm.value
+
+
+def fast_sample_time(seed: int, global_pixel: int, k: int, n: int) -> int:
+    """rtw_fast_sample_time: the time of lattice sample k of n of a pixel on a moving scene, in
+    units of 2^-24 (no GPU needed)."""
+    return lib.rtw_fast_sample_time(capi.U128.of(seed), global_pixel, k, n)
 
 
 def _shard(shard):
@@ -437,6 +472,11 @@ class Session:
 
     def set_scene(self, sph, n_sph, mats, n_mats):
         check(lib.rtw_session_set_scene(self.h, sph, n_sph, mats, n_mats))
+
+    def set_scene_moving(self, sph, n_sph, center1, mats, n_mats):
+        """rtw_session_set_scene_moving: center1 holds 3 doubles per sphere, its centre at time 1
+        (Scene.flatten_moving, bouncing_scene). The fast-mode sample routes then render motion blur."""
+        check(lib.rtw_session_set_scene_moving(self.h, sph, n_sph, center1, mats, n_mats))
 
     def render(self, cam: capi.Camera, samples_sqrt: int, seed: int, out_dev_ptr: int,
                stream: int | None = None, shard=None):

@@ -19,7 +19,10 @@
 // lattice is used up, rtw_session_render_fast_adaptive; --min-samples M and --batch B set the
 // first round's and the later rounds' samples per pixel), --denoise [LEVELS] (fast mode, one
 // device: the frame through the guided a-trous filter, rtw_session_render_fast_denoised; without
-// --adaptive at tolerance 0, so every pixel gets the whole lattice). --preview is accepted and
+// --adaptive at tolerance 0, so every pixel gets the whole lattice), --motion (fast mode, one
+// device: the bouncing scene, the final scene with its small diffuse spheres moving while the
+// shutter is open, rtw_session_set_scene_moving; every fast option and output applies, but
+// --denoise, which the library refuses for a moving scene). --preview is accepted and
 // ignored: the winit window itself (application/mod.rs) is out of scope.
 #include <chrono>
 #include <cstdio>
@@ -48,6 +51,7 @@ struct Config {  // main.rs:13-29
     uint32_t min_samples = 16, batch = 16;
     bool denoise = false;
     uint32_t levels = 5;
+    bool motion = false;
     std::vector<int> devices;  // empty: every visible device (--device-ppm: device 0)
 };
 
@@ -158,6 +162,7 @@ Config parse_args(int argc, char **argv) {
             uint32_t v = 0;
             if (parse_u32(next, v)) c.levels = v;
         }
+        else if (a == "--motion") c.motion = true;
         else if (a == "--min-samples") need(c.min_samples, "--min-samples");
         else if (a == "--batch") need(c.batch, "--batch");
         else if (a == "--help") {
@@ -180,6 +185,7 @@ Config parse_args(int argc, char **argv) {
             std::printf("\t--min-samples M\t:\twith --adaptive: samples every pixel gets first (default 16)\n");
             std::printf("\t--batch B\t:\twith --adaptive: samples per listed pixel and round (default 16)\n");
             std::printf("\t--denoise [L]\t:\tfast mode, one GPU: filter the frame with L a-trous levels (default 5)\n");
+            std::printf("\t--motion\t:\tfast mode, one GPU: the final scene with bouncing spheres and motion blur\n");
             std::exit(0);
         }
     }
@@ -195,6 +201,17 @@ Config parse_args(int argc, char **argv) {
     if (c.denoise && (!c.fast || c.passes || c.devices.size() > 1)) {
         std::fprintf(stderr, "--denoise needs --mode fast on one device, without --passes\n");
         std::exit(1);
+    }
+    if (c.scene == "bouncing") c.motion = true;  // the scene is its motion: never rendered standing still
+    if (c.motion) {
+        if (!c.fast || c.devices.size() > 1) {
+            std::fprintf(stderr, "--motion (--scene bouncing) needs --mode fast on one device\n");
+            std::exit(1);
+        }
+        c.scene = "bouncing";
+        // a moving scene lives in a session: the plain render takes the one-device route whose
+        // PPM text is made on the device (the same file byte for byte)
+        if (!c.png && !c.passes && !c.adaptive && !c.denoise) c.device_ppm = true;
     }
     if ((c.device_ppm || c.png) && c.devices.size() > 1) {  // the frame of a multi-device render is gathered on the host
         std::fprintf(stderr, "%s needs a one-device render: --gpus selects %zu devices\n",

@@ -106,6 +106,8 @@ struct Dielectric final : Material {  // materials.rs:65-73
 struct FlatScene {
     std::vector<rtw_sphere> spheres;
     std::vector<rtw_material> materials;
+    std::vector<double> center1;  // 3 per sphere: its centre at time 1 (rtw_session_set_scene_moving)
+    bool moving = false;          // some sphere's center1 differs from its centre
     std::unordered_map<const Material *, uint32_t> mat_index;  // Arc identity -> table row
     uint32_t intern(const std::shared_ptr<Material> &m);
 };
@@ -117,9 +119,13 @@ struct Sphere final : Hittable {  // sphere.rs:11-37
     Point3 center;
     double radius;
     std::shared_ptr<Material> mat;
-    Sphere(Point3 c, double r, std::shared_ptr<Material> m) : center(c), radius(r), mat(std::move(m)) {}
+    Point3 center1;  // at time 1 (fast-mode motion blur); center for a sphere that stands still
+    Sphere(Point3 c, double r, std::shared_ptr<Material> m) : center(c), radius(r), mat(std::move(m)), center1(c) {}
     static std::shared_ptr<Sphere> new_world_obj(double x, double y, double z, double radius,
                                                  std::shared_ptr<Material> m);
+    // the book's moving sphere: at c0 when the shutter opens (t = 0), at c1 when it closes
+    static std::shared_ptr<Sphere> new_moving_world_obj(Point3 c0, Point3 c1, double radius,
+                                                        std::shared_ptr<Material> m);
     void flatten(FlatScene &out) const override;
 };
 struct Scene final : Hittable {  // hittable.rs:119-143 (objects in insertion order)
@@ -165,7 +171,8 @@ struct BuiltScene {
     Camera cam;
     std::shared_ptr<Scene> world;
 };
-// name: complex | simple | threads | super_simple | three_lambertian
+// name: complex | simple | threads | super_simple | three_lambertian | bouncing (complex
+// with its small Lambertian spheres moving up: rtw_scene_bouncing)
 BuiltScene build_scene(const std::string &name, rtw_u128 seed, uint32_t h, uint32_t w,
                        uint32_t max_depth);
 

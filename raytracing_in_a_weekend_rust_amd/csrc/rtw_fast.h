@@ -33,6 +33,12 @@ struct FastParams {
     uint32_t *cursor;       // pixel hand-out counter (zeroed by the launcher)
     unsigned long long *counters;  // [0] segments, [1] node visits, [2] pixels written, [3] wave iterations,
                                    // [4] wave-level walk iterations
+    // motion blur (last, so every field above keeps its offset): the moving kernels
+    // run when move != 0; bits 8..23 of a mover's kind word hold its row of vel plus one
+    const float4 *vel;   // {vx, vy, vz, 0} per moving sphere, v = f32(center1 - center0)
+    uint32_t n_mov;      // rows of vel
+    uint32_t t_stride;   // rtw_lattice_stride(n_off): sample k's time stratum is (k t_stride) mod n_off
+    uint32_t move, _pad;
 };
 
 constexpr uint32_t kBlock = 512;   // 8 waves per workgroup, two per CU (LDS-bound: 640 measured 25% slower)
@@ -47,8 +53,9 @@ constexpr uint32_t stack_slots(uint32_t depth) { return 3 * depth + 2; }
 
 // Dynamic LDS bytes of a launch: the stacks, plus the scene tables when both fit below
 // the kernel's cap (*scene_in_lds; kLdsCap, kAccLdsCap, kListLdsCap); otherwise the kernel
-// reads the scene from global memory.
-size_t lds_bytes(uint32_t n_sph, uint32_t n_node, uint32_t n_stack, uint32_t cap, bool *scene_in_lds);
+// reads the scene from global memory. n_mov: the velocity rows a moving launch stages too.
+size_t lds_bytes(uint32_t n_sph, uint32_t n_node, uint32_t n_stack, uint32_t cap, bool *scene_in_lds,
+                 uint32_t n_mov = 0);
 
 // Enqueues the render (zeroes the cursor and counters first).
 hipError_t launch(const FastParams &P, int n_cu, hipStream_t st, bool scene_lds = true);

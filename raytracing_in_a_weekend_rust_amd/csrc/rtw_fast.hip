@@ -54,27 +54,34 @@ struct OneShot : RgbSums {
     }
 };
 
-template <bool kLds>
+// kMove: the motion-blur instantiation (rtw_fast_dev.h: Motion)
+template <bool kLds, bool kMove>
 __global__ __launch_bounds__(kBlock, 2) void rtw_fast_render(const FastParams P) {
     OneShot u{{}, P, P.n_rows * P.W};
     uint32_t written;
-    const WaveStats w = run_ring<kLds>(P, u, written);
+    const WaveStats w = run_ring<kLds, kMove>(P, u, written);
     add_counters(P, threadIdx.x & 63u, w, written, false);
 }
 
 }  // namespace
 
-size_t lds_bytes(uint32_t n_sph, uint32_t n_node, uint32_t n_stack, uint32_t cap, bool *scene_in_lds) {
+size_t lds_bytes(uint32_t n_sph, uint32_t n_node, uint32_t n_stack, uint32_t cap, bool *scene_in_lds,
+                 uint32_t n_mov) {
     const size_t stacks = static_cast<size_t>(n_stack) * kBlock * sizeof(uint16_t);
     const size_t scene = static_cast<size_t>(n_sph) * (2 * sizeof(float4) + sizeof(uint32_t)) +
-                         static_cast<size_t>(n_node) * rtw_accel::kNodeF4 * sizeof(float4);
+                         static_cast<size_t>(n_node) * rtw_accel::kNodeF4 * sizeof(float4) +
+                         static_cast<size_t>(n_mov) * sizeof(float4);
     *scene_in_lds = stacks + scene <= cap;
     return *scene_in_lds ? stacks + scene : (stacks ? stacks : 16);
 }
 
 hipError_t launch(const FastParams &P, int n_cu, hipStream_t st, bool scene_lds) {
     // a wave starts on one pixel: no more workgroups than have work
-    return launch_persistent(rtw_fast_render<true>, rtw_fast_render<false>, P, P, P.n_rows == 0 || P.W == 0, 5, kWaves,
+    const bool nothing = P.n_rows == 0 || P.W == 0;
+    if (P.move)
+        return launch_persistent(rtw_fast_render<true, true>, rtw_fast_render<false, true>, P, P, nothing, 5, kWaves,
+                                 kLdsCap, n_cu, st, scene_lds);
+    return launch_persistent(rtw_fast_render<true, false>, rtw_fast_render<false, false>, P, P, nothing, 5, kWaves,
                              kLdsCap, n_cu, st, scene_lds);
 }
 

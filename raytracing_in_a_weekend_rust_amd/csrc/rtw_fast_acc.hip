@@ -33,7 +33,7 @@ namespace rtw_fast {
 namespace {
 
 // ---- a lane owns a pixel (k_count < kAccLaneMax)
-template <bool kLds>
+template <bool kLds, bool kMove>
 __global__ __launch_bounds__(kBlock, 2) void rtw_fast_acc_lane(const AccParams A) {
     extern __shared__ __attribute__((aligned(16))) float4 lds[];
     const FastParams &P = A.f;
@@ -41,7 +41,9 @@ __global__ __launch_bounds__(kBlock, 2) void rtw_fast_acc_lane(const AccParams A
     uint16_t *stk = reinterpret_cast<uint16_t *>(lds) + tid;  // slot j at stk[j * kBlock]
     const float4 *geo, *mat, *nodes;
     const uint32_t *kind;
-    stage_scene<kLds>(P, lds, tid, geo, mat, nodes, kind);
+    Motion mo{};  // kMove: the velocity rows and the time of the lane's sample (rtw_fast_dev.h)
+    stage_scene<kLds, kMove>(P, lds, tid, geo, mat, nodes, kind, &mo.vel);
+    mo.kind = kind;
     const uint64_t npix = static_cast<uint64_t>(P.n_rows) * P.W;
     const float cmax = P.cmax;
     bool exhausted = false;  // wave-uniform: the cursor has passed the last pixel
@@ -69,7 +71,7 @@ __global__ __launch_bounds__(kBlock, 2) void rtw_fast_acc_lane(const AccParams A
             }
         }
         if (pix != kFree && !path) {
-            start_path(P, pix, A.k_first + ki * A.k_step, rng, g);
+            start_path<kMove>(P, pix, A.k_first + ki * A.k_step, rng, g, &mo.t);
             tr = tg = tb = 1.f;
             depth = 0;
             path = true;
@@ -78,8 +80,8 @@ __global__ __launch_bounds__(kBlock, 2) void rtw_fast_acc_lane(const AccParams A
         ++iters;
         // ---- one segment per busy lane
         float cr = 0.f, cg = 0.f, cb = 0.f;
-        if (path && trace_segment(P, geo, mat, kind, nodes, g, rng, tr, tg, tb, depth, stk, segs, visits, wvisits, cr, cg,
-                                  cb)) {
+        if (path && trace_segment<kMove>(P, geo, mat, kind, nodes, g, rng, tr, tg, tb, depth, stk, segs, visits, wvisits,
+                                         cr, cg, cb, mo)) {
             sr += to_fixed(cr, cmax), sg += to_fixed(cg, cmax), sb += to_fixed(cb, cmax);
             path = false;
             if (++ki == A.k_count) {  // the pixel's only writer in this launch
@@ -113,11 +115,11 @@ struct Pass : RgbSums {
     }
 };
 
-template <bool kLds>
+template <bool kLds, bool kMove>
 __global__ __launch_bounds__(kBlock, 2) void rtw_fast_acc_ring(const AccParams A) {
     Pass u{{}, A, A.f.n_rows * A.f.W, {}};
     uint32_t written;
-    const WaveStats w = run_ring<kLds>(A.f, u, written);
+    const WaveStats w = run_ring<kLds, kMove>(A.f, u, written);
     add_counters(A.f, threadIdx.x & 63u, w, written, false);
 }
 
@@ -139,11 +141,14 @@ hipError_t launch_accumulate(const AccParams &A_in, int n_cu, hipStream_t st, bo
     A.chunk = std::min(16u, std::max(1u, 256u / std::max(A.k_count, 1u)));
     const bool nothing = P.n_rows == 0 || P.W == 0 || A.k_count == 0;
     // a wave starts on 64 pixels (lane) or 1 (ring): no more workgroups than have work
-    if (A.k_count < kAccLaneMax)
-        return launch_persistent(rtw_fast_acc_lane<true>, rtw_fast_acc_lane<false>, A, P, nothing, 5, kBlock, kAccLdsCap,
-                                 n_cu, st, scene_lds);
-    return launch_persistent(rtw_fast_acc_ring<true>, rtw_fast_acc_ring<false>, A, P, nothing, 5, kWaves, kAccLdsCap,
-                             n_cu, st, scene_lds);
+    const bool lane = A.k_count < kAccLaneMax;
+    if (P.move)
+        return launch_persistent(lane ? rtw_fast_acc_lane<true, true> : rtw_fast_acc_ring<true, true>,
+                                 lane ? rtw_fast_acc_lane<false, true> : rtw_fast_acc_ring<false, true>, A, P, nothing, 5,
+                                 lane ? kBlock : kWaves, kAccLdsCap, n_cu, st, scene_lds);
+    return launch_persistent(lane ? rtw_fast_acc_lane<true, false> : rtw_fast_acc_ring<true, false>,
+                             lane ? rtw_fast_acc_lane<false, false> : rtw_fast_acc_ring<false, false>, A, P, nothing, 5,
+                             lane ? kBlock : kWaves, kAccLdsCap, n_cu, st, scene_lds);
 }
 
 hipError_t launch_resolve(const unsigned long long *acc, uint64_t n_samples, uint64_t n_pixels, float *out_rgb,

@@ -87,7 +87,7 @@ struct List {
     }
 };
 
-template <bool kLds>
+template <bool kLds, bool kMove>
 __global__ __launch_bounds__(kBlock, 2) void rtw_fast_acc_list(const ListParams A) {
     const FastParams &P = A.f;
     const uint32_t npix = P.n_rows * P.W;
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(kBlock, 2) void rtw_fast_acc_list(const ListParams 
     if (blockIdx.x != 0 && static_cast<uint64_t>(blockIdx.x) * kWaves * chunk >= n_ent) return;
     List u{A, npix, n_ent, chunk, {}};
     uint32_t flushed;
-    const WaveStats w = run_ring<kLds>(P, u, flushed);
+    const WaveStats w = run_ring<kLds, kMove>(P, u, flushed);
     // [2] counts every pixel that needs nothing more from this launch: the served entries, and
     // once the pixels outside the list
     unsigned long long done = u.served;
@@ -225,8 +225,11 @@ hipError_t launch_accumulate_list(const ListParams &A_in, int n_cu, hipStream_t 
     // entries a wave claims per cursor atomic: about 256 samples' worth, never more than 16
     A.chunk = std::min(16u, std::max(1u, 256u / std::max(A.m, 1u)));
     // a wave starts on one pixel: no more workgroups than the shard could give work to
-    return launch_persistent(rtw_fast_acc_list<true>, rtw_fast_acc_list<false>, A, A.f, false, 6, kWaves, kListLdsCap,
-                             n_cu, st, scene_lds);
+    if (A.f.move)
+        return launch_persistent(rtw_fast_acc_list<true, true>, rtw_fast_acc_list<false, true>, A, A.f, false, 6, kWaves,
+                                 kListLdsCap, n_cu, st, scene_lds);
+    return launch_persistent(rtw_fast_acc_list<true, false>, rtw_fast_acc_list<false, false>, A, A.f, false, 6, kWaves,
+                             kListLdsCap, n_cu, st, scene_lds);
 }
 
 hipError_t launch_resolve_counts(const unsigned long long *acc, const uint32_t *counts, uint64_t n_pixels,
@@ -359,8 +362,9 @@ std::string render_adaptive_device(const Camera &cam, const Scene &world, uint32
     };
     try {
         ok(rtw_session_create(device, &s));
-        ok(rtw_session_set_scene(s, flat.spheres.data(), static_cast<uint32_t>(flat.spheres.size()),
-                                 flat.materials.data(), static_cast<uint32_t>(flat.materials.size())));
+        ok(rtw_session_set_scene_moving(s, flat.spheres.data(), static_cast<uint32_t>(flat.spheres.size()),
+                                        flat.moving ? flat.center1.data() : nullptr,  // null: rtw_session_set_scene
+                                        flat.materials.data(), static_cast<uint32_t>(flat.materials.size())));
         const uint32_t w = cam.width(), h = cam.height();
         const uint64_t n = std::max<uint64_t>(static_cast<uint64_t>(w) * h * 3, 1);
         HIPCHECK(hipSetDevice(device));

@@ -70,6 +70,44 @@ struct Seg {
     float ox, oy, oz, ex, ey, ez, tmin;
 };
 
+// Motion blur. A sample has a time t in [0, 1), one register per lane for the
+// whole path, and a moving sphere is at c(t) = fmaf(t, v, c0) per component: sphere_at is the
+// one expression, used by the closest hit and by the shading normal alike. Only movers have a
+// velocity: bits 8..23 of a sphere's kind word hold its row of the velocity table plus one
+// (0: the sphere stands still, and its record is the static kernels'). The static
+// instantiations (kMove = false) read neither the word nor the table nor t.
+struct Motion {
+    const uint32_t *kind;
+    const float4 *vel;
+    float t;
+};
+constexpr uint32_t kKindMask = 3u;  // the material of a kind word
+
+template <bool kMove>
+__device__ __forceinline__ float4 sphere_at(const float4 *__restrict__ geo, const Motion &mo, uint32_t i) {
+    float4 S = geo[i];
+    if constexpr (kMove) {
+        const uint32_t m = (mo.kind[i] >> 8) & 0xffffu;
+        if (m) {
+            const float4 V = mo.vel[m - 1u];
+            S.x = fmaf(mo.t, V.x, S.x), S.y = fmaf(mo.t, V.y, S.y), S.z = fmaf(mo.t, V.z, S.z);
+        }
+    }
+    return S;
+}
+
+// The time of lattice sample k of global pixel gpix (rtw_capi.h, rtw_fast_sample_time): the
+// stratum j = (k g) mod N of [0, 1) rotated by a hash of the pixel. g = P.t_stride and
+// N = P.n_off are wave-uniform; nothing is drawn from the sample's stream.
+__device__ __forceinline__ float sample_time(const FastParams &P, uint64_t gpix, uint32_t k) {
+    const uint32_t N = P.n_off;
+    const uint32_t j = static_cast<uint32_t>(static_cast<uint64_t>(k) * P.t_stride % N);
+    const uint32_t base = static_cast<uint32_t>(((2ull * j + 1ull) << 23) / N);
+    const uint64_t h = fmix64(fmix64(P.seed_mix ^ (gpix * 0x9e3779b97f4a7c15ull)) + (1ull << 32)) >> 40;
+    const uint32_t t24 = (base + static_cast<uint32_t>(h)) & 0xffffffu;
+    return static_cast<float>(t24) * 5.9604644775390625e-08f;  // 2^-24: exact
+}
+
 // Sphere::hit (sphere.rs:39-71) in distance units along the unit direction, with
 // the discriminant from the closest-approach vector (r^2 - |oc - hb e|^2: no
 // cancellation against |oc|^2 for big spheres) and the stable root pair.
@@ -111,20 +149,22 @@ __device__ __forceinline__ void walk_ray(const Seg &g, rtw_accel::WalkRay &r) {
 
 // Closest hit: the "always" spheres, then the BVH walk testing leaf spheres as
 // they are reached (the running best is the walk's cut), or a linear scan.
+template <bool kMove = false>
 __device__ __forceinline__ void scene_hit(const FastParams &P, const float4 *__restrict__ geo,
                                           const float4 *__restrict__ nodes, const Seg &g, float &best,
-                                          int &hid, uint16_t *stk, uint32_t &visits, uint32_t &wvisits) {
+                                          int &hid, uint16_t *stk, uint32_t &visits, uint32_t &wvisits,
+                                          const Motion &mo = Motion{}) {
     best = INFINITY, hid = -1;
     if (P.n_node == 0) {
-        for (uint32_t i = 0; i < P.n_sph; ++i) sphere_test(geo[i], static_cast<int>(i), g, best, hid);
+        for (uint32_t i = 0; i < P.n_sph; ++i) sphere_test(sphere_at<kMove>(geo, mo, i), static_cast<int>(i), g, best, hid);
         return;
     }
     for (uint32_t a = 0; a < P.n_always; ++a) {
         const uint32_t i = P.always[a];
-        sphere_test(geo[i], static_cast<int>(i), g, best, hid);
+        sphere_test(sphere_at<kMove>(geo, mo, i), static_cast<int>(i), g, best, hid);
     }
     if (!(rtw_accel::fmax3(fabsf(g.ox), fabsf(g.oy), fabsf(g.oz)) <= rtw_accel::kGuardBvh)) {
-        for (uint32_t i = 0; i < P.n_sph; ++i) sphere_test(geo[i], static_cast<int>(i), g, best, hid);
+        for (uint32_t i = 0; i < P.n_sph; ++i) sphere_test(sphere_at<kMove>(geo, mo, i), static_cast<int>(i), g, best, hid);
         return;
     }
     rtw_accel::WalkRay r;
@@ -157,7 +197,7 @@ __device__ __forceinline__ void scene_hit(const FastParams &P, const float4 *__r
             const uint32_t j = static_cast<uint32_t>(__builtin_ctz(lmask));
             lmask &= lmask - 1u;
             const uint32_t k = ((j & 2u ? r23w : r01w) >> (16u * (j & 1u))) & 0xffffu;
-            sphere_test(geo[k], static_cast<int>(k), g, best, hid);
+            sphere_test(sphere_at<kMove>(geo, mo, k), static_cast<int>(k), g, best, hid);
         }
         const uint32_t ord = ((oct_hi ? rtw_accel::as_u32(qo.y) : rtw_accel::as_u32(qo.x)) >> oct_shift) & 0xffu;
         const uint64_t refs = (static_cast<uint64_t>(r23w) << 32) | r01w;
@@ -173,11 +213,14 @@ __device__ __forceinline__ void scene_hit(const FastParams &P, const float4 *__r
 }
 
 // get_ray (camera.rs:400-420) for lattice sample k of shard pixel pix: seeds the
-// sample's stream and sets the primary segment.
-__device__ __forceinline__ void start_path(const FastParams &P, uint32_t pix, uint32_t k, Rng &rng, Seg &g) {
+// sample's stream and sets the primary segment; a moving launch also gets the sample's time.
+template <bool kMove = false>
+__device__ __forceinline__ void start_path(const FastParams &P, uint32_t pix, uint32_t k, Rng &rng, Seg &g,
+                                           float *t = nullptr) {
     const uint32_t lr = pix / P.W, x = pix - lr * P.W;
     const uint32_t y = P.row_begin + lr * P.row_step;
     rng = rng_for(P.seed_mix, static_cast<uint64_t>(y) * P.W + x, k);
+    if constexpr (kMove) *t = sample_time(P, static_cast<uint64_t>(y) * P.W + x, k);
     const float fx = static_cast<float>(x), fy = static_cast<float>(y);
     float sx = fmaf(P.dv[0], fy, fmaf(P.du[0], fx, P.p00[0]));
     float sy = fmaf(P.dv[1], fy, fmaf(P.du[1], fx, P.p00[1]));
@@ -207,23 +250,25 @@ __device__ __forceinline__ void start_path(const FastParams &P, uint32_t pix, ui
 
 // One segment of a lane's path (camera.rs:376-398): true when the path ends, with
 // its colour in (cr, cg, cb); otherwise the next segment is in g.
+template <bool kMove = false>
 __device__ __forceinline__ bool trace_segment(const FastParams &P, const float4 *__restrict__ geo,
                                               const float4 *__restrict__ mat, const uint32_t *__restrict__ kind,
                                               const float4 *__restrict__ nodes, Seg &g, Rng &rng, float &tr,
                                               float &tg, float &tb, uint32_t &depth, uint16_t *stk, uint32_t &segs,
-                                              uint32_t &visits, uint32_t &wvisits, float &cr, float &cg, float &cb) {
+                                              uint32_t &visits, uint32_t &wvisits, float &cr, float &cg, float &cb,
+                                              const Motion &mo = Motion{}) {
     if (depth >= P.max_depth) return true;  // black at the depth cap
     float best;
     int hid;
     ++segs;
-    scene_hit(P, geo, nodes, g, best, hid, stk, visits, wvisits);
+    scene_hit<kMove>(P, geo, nodes, g, best, hid, stk, visits, wvisits, mo);
     if (hid < 0) {
         const float a = 0.5f * (g.ey + 1.f);  // sky (camera.rs:392-396)
         cr = tr * ((1.f - a) + a * 0.5f), cg = tg * ((1.f - a) + a * 0.7f), cb = tb;
         return true;
     }
-    const float4 S = geo[hid], M = mat[hid];
-    const uint32_t kd = kind[hid];
+    const float4 S = sphere_at<kMove>(geo, mo, static_cast<uint32_t>(hid)), M = mat[hid];
+    const uint32_t kd = kMove ? kind[hid] & kKindMask : kind[hid];
     const float px = fmaf(best, g.ex, g.ox), py = fmaf(best, g.ey, g.oy), pz = fmaf(best, g.ez, g.oz);
     const float ir = __builtin_amdgcn_rcpf(S.w);
     float nx = (px - S.x) * ir, ny = (py - S.y) * ir, nz = (pz - S.z) * ir;
@@ -276,14 +321,22 @@ __device__ __forceinline__ unsigned long long to_fixed(float c, float cmax) {
 }
 
 // Scene tables and the BVH into LDS behind the per-lane stacks.
-template <bool kLds>
+// A moving launch keeps its velocity rows between the nodes and the kind words (16-aligned).
+template <bool kLds, bool kMove = false>
 __device__ __forceinline__ void stage_scene(const FastParams &P, float4 *lds, uint32_t tid, const float4 *&geo,
-                                            const float4 *&mat, const float4 *&nodes, const uint32_t *&kind) {
+                                            const float4 *&mat, const float4 *&nodes, const uint32_t *&kind,
+                                            const float4 **vel = nullptr) {
     geo = P.geo, mat = P.mat, nodes = P.nodes, kind = P.kind;
+    if constexpr (kMove) *vel = P.vel;
     if constexpr (kLds) {
         float4 *g = lds + P.n_stack * kBlock * sizeof(uint16_t) / sizeof(float4);
         float4 *m = g + P.n_sph, *nd = m + P.n_sph;
-        uint32_t *kd = reinterpret_cast<uint32_t *>(nd + P.n_node * rtw_accel::kNodeF4);
+        float4 *tail = nd + P.n_node * rtw_accel::kNodeF4;
+        if constexpr (kMove) {
+            for (uint32_t i = tid; i < P.n_mov; i += kBlock) tail[i] = P.vel[i];
+            *vel = tail, tail += P.n_mov;
+        }
+        uint32_t *kd = reinterpret_cast<uint32_t *>(tail);
         for (uint32_t i = tid; i < P.n_sph; i += kBlock) g[i] = P.geo[i], m[i] = P.mat[i], kd[i] = P.kind[i];
         for (uint32_t i = tid; i < P.n_node * rtw_accel::kNodeF4; i += kBlock) nd[i] = P.nodes[i];
         geo = g, mat = m, nodes = nd, kind = kd;
@@ -369,7 +422,7 @@ struct RgbSums {
 
 // Runs the calling wave until the cursor is exhausted and its ring is empty; returns its
 // counts and, in flushed, the jobs it flushed. Every wave of the workgroup must call it.
-template <bool kLds, class Use>
+template <bool kLds, bool kMove, class Use>
 __device__ __forceinline__ WaveStats run_ring(const FastParams &P, Use &u, uint32_t &flushed) {
     using Job = typename Use::Job;
     constexpr uint32_t kRing = Use::kRing;
@@ -380,7 +433,9 @@ __device__ __forceinline__ WaveStats run_ring(const FastParams &P, Use &u, uint3
     uint16_t *stk = reinterpret_cast<uint16_t *>(lds) + tid;
     const float4 *geo, *mat, *nodes;
     const uint32_t *kind;
-    stage_scene<kLds>(P, lds, tid, geo, mat, nodes, kind);
+    Motion mo{};
+    stage_scene<kLds, kMove>(P, lds, tid, geo, mat, nodes, kind, &mo.vel);
+    mo.kind = kind;
     const float cmax = P.cmax;
     // wave-uniform ring state
     Job jobs[kRing], cur{};
@@ -425,7 +480,7 @@ __device__ __forceinline__ WaveStats run_ring(const FastParams &P, Use &u, uint3
             const uint32_t rank = rank_in(need);
             const uint32_t avail = u.count(cur) - next;
             if (slot == kFree && rank < avail) {
-                start_path(P, cur.pix, u.lattice(cur, next + rank), rng, g);
+                start_path<kMove>(P, cur.pix, u.lattice(cur, next + rank), rng, g, &mo.t);
                 tr = tg = tb = 1.f;
                 depth = 0;
                 slot = cs;
@@ -440,8 +495,8 @@ __device__ __forceinline__ WaveStats run_ring(const FastParams &P, Use &u, uint3
         ++w.iters;
         // ---- one segment per busy lane; finished samples into their job's sums
         float cr = 0.f, cg = 0.f, cb = 0.f;
-        const bool fin = slot != kFree && trace_segment(P, geo, mat, kind, nodes, g, rng, tr, tg, tb, depth, stk, w.segs,
-                                                        w.visits, w.wvisits, cr, cg, cb);
+        const bool fin = slot != kFree && trace_segment<kMove>(P, geo, mat, kind, nodes, g, rng, tr, tg, tb, depth, stk,
+                                                               w.segs, w.visits, w.wvisits, cr, cg, cb, mo);
         if (fin) Use::add(acc[wave][slot], to_fixed(cr, cmax), to_fixed(cg, cmax), to_fixed(cb, cmax));
 #pragma unroll
         for (uint32_t s = 0; s < kRing; ++s)
@@ -498,7 +553,7 @@ hipError_t launch_persistent(void (*in_lds_kernel)(Params), void (*global_kernel
     const uint32_t blocks = static_cast<uint32_t>(
         std::min<uint64_t>(static_cast<uint64_t>(n_cu > 0 ? n_cu : 256) * 2, (npix + per_block - 1) / per_block));
     bool in_lds = false;
-    size_t lds = lds_bytes(P.n_sph, P.n_node, P.n_stack, cap, &in_lds);
+    size_t lds = lds_bytes(P.n_sph, P.n_node, P.n_stack, cap, &in_lds, P.move ? P.n_mov : 0u);
     if (!scene_lds && in_lds) {
         in_lds = false;
         lds = P.n_stack ? static_cast<size_t>(P.n_stack) * kBlock * sizeof(uint16_t) : 16;

@@ -508,8 +508,9 @@ std::string render_ppm_device(const Camera &cam, const Scene &world, uint32_t sa
     };
     try {
         ok(rtw_session_create(device, &s));
-        ok(rtw_session_set_scene(s, flat.spheres.data(), static_cast<uint32_t>(flat.spheres.size()),
-                                 flat.materials.data(), static_cast<uint32_t>(flat.materials.size())));
+        ok(rtw_session_set_scene_moving(s, flat.spheres.data(), static_cast<uint32_t>(flat.spheres.size()),
+                                        flat.moving ? flat.center1.data() : nullptr,  // null: rtw_session_set_scene
+                                        flat.materials.data(), static_cast<uint32_t>(flat.materials.size())));
         const uint64_t n = static_cast<uint64_t>(cam.width()) * cam.height() * 3;
         HIPCHECK(hipSetDevice(device));
         HIPCHECK(hipMalloc(&d_fb, std::max<uint64_t>(n, 1) * (fast ? sizeof(float) : sizeof(double))));

@@ -2509,6 +2509,11 @@ struct rtw_session {
     float4 *d_fgeo = nullptr, *d_fmat = nullptr;
     uint32_t *d_fkind = nullptr, *d_fcursor = nullptr;
     unsigned long long *d_fcount = nullptr;
+    // motion blur (rtw_session_set_scene_moving): the movers' velocity rows; moving scenes
+    // render in fast mode only, through the moving kernels (rtw_fast_dev.h: Motion)
+    float4 *d_fvel = nullptr;
+    uint32_t n_mov = 0;
+    bool moving = false;
     bool last_fast = false;
     bool last_list = false;  // the last fast launch was a list accumulate: samples come from its counter
     // adaptive fast mode's driver (rtw_fast_adapt.h): sums, moments, counts, list (grow-only),
@@ -2598,12 +2603,29 @@ struct SceneStage {
     }
 };
 
-void set_scene(rtw_session *s, const rtw_sphere *sp, uint32_t n, const rtw_material *m, uint32_t nm) {
+// center1 (nullable, n x 3): the spheres' centres at time 1 (rtw_session_set_scene_moving).
+// A sphere whose v = f32(center1 - center0) is not zero is a mover; without one this is the
+// static scene, table for table.
+void set_scene(rtw_session *s, const rtw_sphere *sp, uint32_t n, const rtw_material *m, uint32_t nm,
+               const double *center1 = nullptr) {
     validate_scene(sp, n, m, nm);
+    if (n && !sp) center1 = nullptr;
+    std::vector<float4> vel;          // a row per mover
+    std::vector<uint32_t> mover(n, 0);  // its row + 1, 0 for a sphere that stands still
+    for (uint32_t i = 0; center1 && i < n; ++i) {
+        float v[3];
+        for (int k = 0; k < 3; ++k) v[k] = static_cast<float>(center1[3 * i + k] - sp[i].center[k]);
+        if (v[0] != 0.f || v[1] != 0.f || v[2] != 0.f) {
+            vel.push_back(make_float4(v[0], v[1], v[2], 0.f));
+            mover[i] = static_cast<uint32_t>(vel.size());
+        }
+    }
+    const bool moving = !vel.empty();
     HIPCHECK(hipSetDevice(s->device));
     if (s->pending) HIPCHECK(hipEventSynchronize(s->ev1));  // a render may still read the arena
     SceneStage stage;
     s->d_fgeo = s->d_fmat = nullptr, s->d_fkind = nullptr;
+    s->d_fvel = nullptr, s->n_mov = 0, s->moving = false;
     s->d_sph = nullptr, s->d_filt = nullptr;
     s->d_shade = nullptr, s->d_nbr = nullptr, s->n_nbr = 0, s->d_trap = nullptr;
     s->d_nodes = nullptr, s->d_leaves = nullptr, s->d_always = nullptr;
@@ -2685,6 +2707,20 @@ void set_scene(rtw_session *s, const rtw_sphere *sp, uint32_t n, const rtw_mater
             for (int k = 0; k < 3; ++k) cen[3 * i + k] = sp[i].center[k];
             rad[i] = sp[i].radius;
             r2p[i] = f[i].w;
+            if (!mover[i]) continue;
+            // a mover enters the builder as the bounding sphere of its sweep: centre
+            // (c0 + c1) / 2, radius |r| + |c1 - c0| / 2, plus a margin of 2^-20 of the largest
+            // coordinate for the roundings of f32(c0), f32(c1 - c0) and fmaf (three half ulps
+            // of at most 2^-24 of that coordinate each: DESIGN 3.13)
+            double d2 = 0., big = 0.;
+            for (int k = 0; k < 3; ++k) {
+                const double c0 = sp[i].center[k], c1 = center1[3 * i + k];
+                cen[3 * i + k] = 0.5 * (c0 + c1);
+                d2 += (c1 - c0) * (c1 - c0);
+                big = std::max(big, std::max(std::fabs(c0), std::fabs(c1)));
+            }
+            rad[i] = std::fabs(sp[i].radius) + 0.5 * std::sqrt(d2) + big * (1. / 1048576.);
+            r2p[i] = rtw_accel::filter_r2p(&cen[3 * i], rad[i] * rad[i]);
         }
         rtw_accel::Bvh bvh;
         if (n && rtw_accel::build(cen.data(), rad.data(), r2p.data(), n, bvh)) {
@@ -2717,11 +2753,12 @@ void set_scene(rtw_session *s, const rtw_sphere *sp, uint32_t n, const rtw_mater
                                     static_cast<float>(M.albedo[2]),
                                     M.kind == RTW_METAL ? static_cast<float>(M.fuzz) : 0.f);
             }
-            fk[i] = M.kind;
+            fk[i] = M.kind | (mover[i] << 8);  // bits 8..23: the mover's velocity row + 1
         }
         stage.add(&s->d_fgeo, fg.data(), fg.size());
         stage.add(&s->d_fmat, fm.data(), fm.size());
         stage.add(&s->d_fkind, fk.data(), fk.size());
+        if (moving) stage.add(&s->d_fvel, vel.data(), vel.size());
     }
     stage.upload(s);
     s->att_finite = true;
@@ -2732,7 +2769,17 @@ void set_scene(rtw_session *s, const rtw_sphere *sp, uint32_t n, const rtw_mater
     }
     s->n_sph = n;
     s->n_mats = nm;
+    s->n_mov = static_cast<uint32_t>(vel.size());
+    s->moving = moving;
     s->scene_set = true;
+}
+
+// What a moving scene cannot serve says so before any device work.
+void refuse_moving(const rtw_session *s, const char *what) {
+    if (s->moving)
+        throw rtw::Error(RTW_E_UNSUPPORTED, std::string(what) + ": the session's scene has moving spheres "
+                                            "(rtw_session_set_scene_moving); motion blur is rendered by "
+                                            "the fast-mode sample routes only");
 }
 
 rtw_shard resolve_shard(const rtw_camera *cam, const rtw_shard *shard) {
@@ -2765,6 +2812,7 @@ void render(rtw_session *s, const rtw_camera *cam, uint32_t samples_sqrt, rtw_u1
     if (!cam || !out) throw rtw::Error(RTW_E_ARG, "null argument");
     const rtw::Knobs kn;  // tuning only under RTW_AB (rtw_internal.h)
     if (!s->scene_set) throw rtw::Error(RTW_E_ARG, "session has no scene");
+    refuse_moving(s, "rtw_session_render (f64 parity)");
     if (cam->img_height == 0 || cam->img_width == 0)
         throw rtw::Error(RTW_E_EMPTY_IMAGE, "image height and width must be > 0");  // camera.rs:267
     if (samples_sqrt > 65535) throw rtw::Error(RTW_E_UNSUPPORTED, "samples_sqrt > 65535");
@@ -3219,6 +3267,12 @@ rtw_fast::FastParams fast_params(rtw_session *s, const rtw_camera *cam, uint32_t
     F.geo = s->d_fgeo, F.mat = s->d_fmat, F.kind = s->d_fkind;
     F.cursor = s->d_fcursor;
     F.counters = s->d_fcount;
+    // motion blur: the moving kernels for a moving scene, or for any scene with RTW_FAST_MOVE=1
+    // under RTW_AB (A/B: the cost of the variant itself; no kind word then names a velocity row)
+    const char *move_knob = rtw::Knobs().get("RTW_FAST_MOVE");
+    F.move = s->moving || (move_knob && std::atoi(move_knob)) ? 1u : 0u;
+    F.vel = s->d_fvel, F.n_mov = s->n_mov;
+    F.t_stride = rtw_lattice_stride(F.n_off);
     return F;
 }
 
@@ -3267,7 +3321,7 @@ void render_fast(rtw_session *s, const rtw_camera *cam, uint32_t samples_sqrt, r
     const bool scene_lds = begin_fast(s, st);
     HIPCHECK(rtw_fast::launch(F, s->n_cu, st, scene_lds));
     bool in_lds = false;
-    finish_fast(s, F, F.n_off, static_cast<uint32_t>(rtw_fast::lds_bytes(F.n_sph, F.n_node, F.n_stack, rtw_fast::kLdsCap, &in_lds)), st);
+    finish_fast(s, F, F.n_off, static_cast<uint32_t>(rtw_fast::lds_bytes(F.n_sph, F.n_node, F.n_stack, rtw_fast::kLdsCap, &in_lds, F.move ? F.n_mov : 0u)), st);
 }
 
 // Progressive fast mode (rtw_fast_acc.hip): lattice samples k_first + i k_step, i < k_count,
@@ -3290,7 +3344,7 @@ void accumulate_fast(rtw_session *s, const rtw_camera *cam, uint32_t samples_sqr
     HIPCHECK(rtw_fast::launch_accumulate(A, s->n_cu, st, scene_lds));
     if (k_count == 0) A.f.n_rows = 0;  // nothing launched, nothing flushed: the latch expects 0 pixels
     bool in_lds = false;
-    finish_fast(s, A.f, k_count, static_cast<uint32_t>(rtw_fast::lds_bytes(A.f.n_sph, A.f.n_node, A.f.n_stack, rtw_fast::kAccLdsCap, &in_lds)), st);
+    finish_fast(s, A.f, k_count, static_cast<uint32_t>(rtw_fast::lds_bytes(A.f.n_sph, A.f.n_node, A.f.n_stack, rtw_fast::kAccLdsCap, &in_lds, A.f.move ? A.f.n_mov : 0u)), st);
 }
 
 // Adaptive fast mode (rtw_fast_adapt.hip): the next m samples, in the order i -> (i k_mul) mod N,
@@ -3315,7 +3369,7 @@ void accumulate_fast_list(rtw_session *s, const rtw_camera *cam, uint32_t sample
     const bool scene_lds = begin_fast(s, st);
     HIPCHECK(rtw_fast::launch_accumulate_list(A, s->n_cu, st, scene_lds));
     bool in_lds = false;
-    finish_fast(s, A.f, 0, static_cast<uint32_t>(rtw_fast::lds_bytes(A.f.n_sph, A.f.n_node, A.f.n_stack, rtw_fast::kListLdsCap, &in_lds)), st);
+    finish_fast(s, A.f, 0, static_cast<uint32_t>(rtw_fast::lds_bytes(A.f.n_sph, A.f.n_node, A.f.n_stack, rtw_fast::kListLdsCap, &in_lds, A.f.move ? A.f.n_mov : 0u)), st);
     s->last_list = true;
 }
 
@@ -3327,6 +3381,7 @@ void collect(rtw_session *s);
 void guides_fast(rtw_session *s, const rtw_camera *cam, const rtw_shard *shard_in, float *guides, hipStream_t st) {
     if (!cam || !guides) throw rtw::Error(RTW_E_ARG, "null argument");
     if (reinterpret_cast<uintptr_t>(guides) % 16) throw rtw::Error(RTW_E_ARG, "guides buffer not 16-byte aligned");
+    refuse_moving(s, "rtw_session_guides_fast (a first hit at one instant is no guide for a blurred pixel)");
     rtw_fast::GuideParams A{};
     A.f = fast_params(s, cam, 0, rtw_u128{0, 0}, shard_in);
     if (s->n_sph >= (1u << 30)) throw rtw::Error(RTW_E_UNSUPPORTED, "guides: 2^30 spheres or more");
@@ -3348,6 +3403,7 @@ void render_fast_adaptive(rtw_session *s, const rtw_camera *cam, uint32_t sample
                           uint32_t batch, float *out, uint32_t *counts_out, hipStream_t st, rtw_adaptive_info *info,
                           const rtw_denoise_params *dn = nullptr, float *out_var = nullptr, double *denoise_ms = nullptr) {
     if (!cam || !out) throw rtw::Error(RTW_E_ARG, "null argument");
+    if (dn) refuse_moving(s, "rtw_session_render_fast_denoised (its guides are first hits at one instant)");
     if (batch == 0 || batch > 65535) throw rtw::Error(RTW_E_ARG, "batch outside 1..65535");
     if (tol_q16 > 65535u || floor_q16 > (1u << 24)) throw rtw::Error(RTW_E_ARG, "tol_q16 > 65535 or floor_q16 > 2^24");
     const rtw_fast::FastParams F = fast_params(s, cam, samples_sqrt, seed, shard_in);  // the checks, and the shard
@@ -3710,6 +3766,15 @@ int rtw_session_set_scene(rtw_session *s, const rtw_sphere *spheres, uint32_t n_
     if (!s) return rtw::set_error("null session"), RTW_E_ARG;
     RTW_GUARD_BEGIN
     set_scene(s, spheres, n_spheres, mats, n_mats);
+    return RTW_OK;
+    RTW_GUARD_END
+}
+
+int rtw_session_set_scene_moving(rtw_session *s, const rtw_sphere *spheres, uint32_t n_spheres, const double *center1,
+                                 const rtw_material *mats, uint32_t n_mats) {
+    if (!s) return rtw::set_error("null session"), RTW_E_ARG;
+    RTW_GUARD_BEGIN
+    set_scene(s, spheres, n_spheres, mats, n_mats, center1);
     return RTW_OK;
     RTW_GUARD_END
 }
